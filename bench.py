@@ -2,19 +2,30 @@
 """Headline benchmark: BASELINE.json config[1] -- union of sphere/box/torus, targetError = 1e-5,
 Create() on the GPU(s) and Query() over 10 M SplitMix64(12345) points per GPU, resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one batched Query() pass over this rank's 10 M points (the data-parallel leg of the
 metric; weak scaling: every rank queries its own 10 M points against the replicated tree, no
-collective).  Create() -- sharded over the ranks with one RCCL all-gather per round -- is timed in the
-same run and reported as create_ms next to it.  Rank 0 prints ONE JSON line.
+collective).  Create() is timed in the same run and reported as create_ms next to it.  Rank 0 prints
+ONE JSON line.
+
+A plain run does only that: it builds the tree, warms up, times the K steps and prints the line.
+--dump-outputs DIR then writes what the last timed step returned (DIR/query_distance.npy, float64;
+a fixed seeded sample when the output is larger than 32 MiB), so that two builds can be compared
+output for output: with the same arguments the inputs are the same from run to run.
 
 roofline: the dominant kernel is query_kernel, HBM-bound, 32 algorithmic bytes per point
 (24 in + 8 out); its average launch duration is measured live with events on the
-stream it is launched on.  cpu_baseline: the CPU oracle ("port", one core) on the same points,
-rank 0 at N = 1 only -- the only leg that touches oracle/ (it also checks a sample of the timed GPU outputs
-against it); the oracle is never the measured path.
+stream it is launched on.
+
+--full adds everything else, each after the timed steps: the one-batch loop (repeated_batch), the
+check of the timed kernel against the host-answered Query, Create() sharded over the ranks with one
+RCCL all-gather per round (N > 1), the cell-sorted locality ceiling, the refined tree, the mesh
+leg, the fit micro-benchmark and cpu_baseline: the CPU oracle ("port", one core) on the same points,
+rank 0 at N = 1 only -- the only leg that touches oracle/ (it also checks a sample of the timed GPU
+outputs against it); the oracle is never the measured path.  The --no-* options switch single legs
+of --full off.
 """
 import argparse
 import json
@@ -36,6 +47,8 @@ N_POINTS = 10_000_000
 TARGET = 1e-5
 JOBS_PER_ROUND = 1024
 CREATE_REPS = 21  # Create() repetitions behind create_ms (their median)
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: at most this many float64 values (32 MiB), a fixed seeded sample of a larger output
+DUMP_SEED = 20261016
 
 
 def splitmix64_points(n, seed=12345):
@@ -73,6 +86,17 @@ def counter_record(name, keys):
     except Exception:  # noqa: BLE001  (no record: nulls)
         pass
     return out
+
+
+def dump_outputs(path, d_out, n):
+    """DIR/query_distance.npy: the signed distances the last timed step wrote to d_out -- all n of them, or the DUMP_SAMPLE values at
+    a fixed seeded set of indices (ascending) when n is larger."""
+    os.makedirs(path, exist_ok=True)
+    vals = d_out[:n]
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        vals = vals[torch.from_numpy(idx).to(d_out.device)]
+    np.save(os.path.join(path, "query_distance.npy"), vals.cpu().numpy().astype(np.float64))
 
 
 def visible_gpus():
@@ -143,17 +167,23 @@ def main():
     ap.add_argument("--points", type=int, default=N_POINTS, help="query points per GPU")
     ap.add_argument("--batches", type=int, default=4, help="distinct point batches the timed Query steps walk through (1 = the same "
                     "batch every step, which the 256 MB Infinity Cache then holds)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fit-bench", action="store_true", help="skip the steady-state fit micro-benchmark (fit_microbench)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/query_distance.npy (float64; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also run every secondary measurement and check (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline (cpu_baseline)")
+    ap.add_argument("--no-fit-bench", action="store_true", help="--full: skip the steady-state fit micro-benchmark (fit_microbench)")
     ap.add_argument("--no-refined", action="store_true",
-                    help="skip the extra Query / QueryWithGradient timings on the refined tree (union3 @ 1e-7)")
+                    help="--full: skip the extra Query / QueryWithGradient timings on the refined tree (union3 @ 1e-7)")
     ap.add_argument("--mesh", default="torus",
-                    help="Create() on a mesh field (BASELINE configs 2-4 shape; dragon.obj / Ramesses.obj are not in the reference "
-                         "mount): 'torus' = displaced torus grid, 2 097 152 triangles (the north_star's 2 M-triangle mesh); "
+                    help="--full: Create() on a mesh field (BASELINE configs 2-4 shape; dragon.obj / Ramesses.obj are not among the "
+                         "reference's files): 'torus' = displaced torus grid, 2 097 152 triangles (the north_star's 2 M-triangle mesh); "
                          "an integer L = bumpy icosphere of subdivision level L (7 = 327 680, 8 = 1 310 720); 'none' = skip")
     ap.add_argument("--no-sorted-ceiling", action="store_true",
-                    help="skip Query on the same points sorted by depth-4 cell (locality ceiling, SURVEY 8d)")
+                    help="--full: skip Query on the same points sorted by depth-4 cell (locality ceiling, SURVEY 8d)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -191,8 +221,8 @@ def main():
 
         # ---------------- Create(): sharded over the ranks, timed over a few repetitions
         # N > 1: create_ms is the policy a user gets by default ("auto": an analytic field is cheap, so every rank
-        # builds the whole tree and nothing is exchanged); create_sharded_ms forces the sharded frontier with its
-        # all-gather per round (the mesh-field path), whose fixed costs exceed this 0.3 ms build.
+        # builds the whole tree and nothing is exchanged); create_sharded_ms (--full) forces the sharded frontier with
+        # its all-gather per round (the mesh-field path), whose fixed costs exceed this 0.3 ms build.
         def timed_create(policy):
             def create():
                 return D.create_distributed(ctx, cfg, field, JOBS_PER_ROUND, policy=policy) if world > 1 else \
@@ -264,35 +294,39 @@ def main():
             t = torch.tensor([wall], device="cuda", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             wall = float(t.item())
+        if args.dump_outputs and rank == 0:  # d_out holds what the last timed step returned (before anything below overwrites it)
+            dump_outputs(args.dump_outputs, d_out, n)
 
-        # the same kernel over ONE batch again and again (what rounds 1-4 timed; see above)
-        def again():
-            tree.query_device(d_xyz.data_ptr(), n, d_out.data_ptr())
-        for _ in range(3):
-            again()
-        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        r0.record(stream)
-        for _ in range(20):
-            again()
-        r1.record(stream)
-        torch.cuda.synchronize()
-        repeated_ms = r0.elapsed_time(r1) / 20
-        # sanity: the output is the real answer (spot parity against the oracle on rank 0; d_out now holds the first batch's values)
-        got = d_out[:: max(1, n // 2000)].cpu().numpy()
-        # ... and on EVERY rank, with or without the CPU-baseline leg, a cross-check that needs no oracle: the timed
-        # kernel's values against the library's other implementation of Query -- calls of <= 32 points are answered on the calling thread
-        # (csrc/host_query.cpp: the same statements compiled for the host) -- on 16 strided groups of 32 points, bit for bit
-        stride_g = max(1, (n - 32) // 16)
-        for g0 in range(0, n - 31, stride_g):
-            pts32 = d_xyz[g0:g0 + 32].cpu().numpy()
-            assert np.array_equal(tree.query(pts32).view(np.uint64), d_out[g0:g0 + 32].cpu().numpy().view(np.uint64)), \
-                "the timed Query kernel and the host-answered Query disagree (rank %d, points %d..)" % (rank, g0)
+        repeated_ms, got = None, None
+        if args.full:
+            # the same kernel over ONE batch again and again (what rounds 1-4 timed; see above)
+            def again():
+                tree.query_device(d_xyz.data_ptr(), n, d_out.data_ptr())
+            for _ in range(3):
+                again()
+            r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            r0.record(stream)
+            for _ in range(20):
+                again()
+            r1.record(stream)
+            torch.cuda.synchronize()
+            repeated_ms = r0.elapsed_time(r1) / 20
+            # sanity: the output is the real answer (spot parity against the oracle on rank 0; d_out now holds the first batch's values)
+            got = d_out[:: max(1, n // 2000)].cpu().numpy()
+            # ... and on EVERY rank, with or without the CPU-baseline leg, a cross-check that needs no oracle: the timed
+            # kernel's values against the library's other implementation of Query -- calls of <= 32 points are answered on the calling
+            # thread (csrc/host_query.cpp: the same statements compiled for the host) -- on 16 strided groups of 32 points, bit for bit
+            stride_g = max(1, (n - 32) // 16)
+            for g0 in range(0, n - 31, stride_g):
+                pts32 = d_xyz[g0:g0 + 32].cpu().numpy()
+                assert np.array_equal(tree.query(pts32).view(np.uint64), d_out[g0:g0 + 32].cpu().numpy().view(np.uint64)), \
+                    "the timed Query kernel and the host-answered Query disagree (rank %d, points %d..)" % (rank, g0)
 
         # ---------------- Create() with the frontier sharded over the ranks (one all-gather per round).  Behind the headline leg and
         # inside a try: this is the part of the run that needs RCCL to take an in-place all-gather on the library's stream, which no
         # box this was developed on could exercise with more than one GPU -- if it fails, the line still carries the weak-scaling Query
         # numbers and says what went wrong instead of taking the whole record down.
-        if world > 1:
+        if world > 1 and args.full:
             try:
                 block_s, st_s, create_sharded_ms, _, per_rank = timed_create("shard")
                 assert block_s == block, "sharded and replicated Create disagree"
@@ -304,7 +338,7 @@ def main():
 
         # locality ceiling: the same points sorted by depth-4 cell, so neighbouring lanes share tree lines
         sorted_ms = None
-        if rank == 0 and not args.no_sorted_ceiling:
+        if args.full and rank == 0 and not args.no_sorted_ceiling:
             def by_cell(x):
                 cell = ((x + 0.5) * 16.0).floor().clamp_(0, 15).to(torch.int64)
                 o = torch.argsort(cell[:, 0] * 256 + cell[:, 1] * 16 + cell[:, 2])
@@ -332,7 +366,7 @@ def main():
         # (union3 @ 1e-7: ~12 k nodes, degrees 2-4, depths 4-6) -- Query goes through
         # query_general_kernel there -- and QueryWithGradient (reference benchmark HPBenchmarks.cpp:169-203).
         refined = None
-        if rank == 0 and not args.no_refined:
+        if args.full and rank == 0 and not args.no_refined:
             import ctypes as C
             blk_r, st_r = H.create_block(ctx, H.make_config(1e-7), field, JOBS_PER_ROUND)
             create_r_all = []
@@ -384,7 +418,7 @@ def main():
             del d_grad, d_out2
 
         mesh = None
-        if args.mesh != "none":
+        if args.full and args.mesh != "none":
             # BASELINE configs 2-4 in shape: a closed triangle mesh as the field, root = mesh box, targetError 1e-5 and
             # 1e-6; with N > 1 ranks the frontier is sharded (one all-gather per round, hpsdf_create_distributed).
             sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -457,7 +491,7 @@ def main():
             del mfield
 
         fit = None
-        if not args.no_fit_bench and rank == 0:
+        if args.full and not args.no_fit_bench and rank == 0:
             # Steady-state fit micro-benchmark: from-scratch fits of a lattice of depth-5 cells, per degree; the
             # default bit-exact kernel and the opt-in matrix-core kernel (hpsdf_ctx_set_fast_fit, degrees 4..9), each with
             # the headline field and with a field that costs nothing (contraction only).  Algorithmic flops:
@@ -556,13 +590,6 @@ def main():
                                "the points come from HBM and not from the 256 MB Infinity Cache" % (n, len(batches)),
                    "jobs_per_round": JOBS_PER_ROUND, "points_per_gpu": n, "sharding": "replicated tree, points split",
                    "point_batches": len(batches)},
-        # one batch queried again and again: its 240 MB stay in the 256 MB Infinity Cache between launches (results bypass it), so this
-        # is NOT an HBM figure -- reported because rounds 1-4 timed it this way and a caller re-querying one batch sees it
-        "repeated_batch": {"avg_launch_ms": repeated_ms, "mpts_per_s": n / repeated_ms / 1e3,
-                           "algorithmic_gbps": 32.0 * n / (repeated_ms * 1e-3) / 1e9,
-                           "note": "one 10 M batch queried again and again, as rounds 1-4 timed `value` (r04: 90.4 Gpts/s with plain result stores): "
-                                   "the points are served from the Infinity Cache, so this is not priced against HBM; `value` walks "
-                                   "config.point_batches distinct batches"},
         "create_ms": create_ms, "create_sharded_ms": create_sharded_ms, "create_sharded": create_sharded,
         "create": {"nodes": stats["n_nodes"], "leaves": stats["n_leaves"], "coeffs": stats["n_coeffs"],
                    "rounds": stats["rounds"], "jobs": stats["jobs"], "fits": stats["fits"], "samples": stats["samples"],
@@ -577,6 +604,14 @@ def main():
                      "l2_to_l1_fill": {"bytes_per_point": 160, "achieved_gbps_per_cu": 160.0 * n / (kernel_ms * 1e-3) / 1e9 / 256,
                                        "measured_ceiling_gbps_per_cu": [66, 73]}},
     }
+    if repeated_ms is not None:
+        # one batch queried again and again: its 240 MB stay in the 256 MB Infinity Cache between launches (results bypass it), so this
+        # is NOT an HBM figure -- reported because rounds 1-4 timed it this way and a caller re-querying one batch sees it
+        out["repeated_batch"] = {"avg_launch_ms": repeated_ms, "mpts_per_s": n / repeated_ms / 1e3,
+                                 "algorithmic_gbps": 32.0 * n / (repeated_ms * 1e-3) / 1e9,
+                                 "note": "one 10 M batch queried again and again, as rounds 1-4 timed `value` (r04: 90.4 Gpts/s with plain result "
+                                         "stores): the points are served from the Infinity Cache, so this is not priced against HBM; `value` walks "
+                                         "config.point_batches distinct batches"}
     refined_check = None
     if refined is not None:
         refined_check = (refined.pop("_blk"), refined.pop("_got"))
@@ -588,7 +623,7 @@ def main():
         out["mesh_create"] = mesh
     if fit:
         out["fit_microbench"] = fit
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # The cpu_baseline leg -- the one place this file touches oracle/: the CPU restatement timed on the host's cores, and,
         # since it is here, the timed GPU outputs checked against it (a sample of the 10 M values of both trees, bit for bit).
         import oracle as O

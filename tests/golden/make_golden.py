@@ -4,6 +4,8 @@ reference-table hashes; everything else comes from the oracle).
   tables.json   SHA-256 of the reference's own constant tables, obtained by compiling the
                 reference headers Include/HP/Utility.h + Include/HP/Legendre.h where they lie
                 (oracle/_ref/libref_tables.so) -- values, not source text.
+  ref_tables.npz  the same tables' values and the reference's scalars (ref_scalars), so that the
+                bitwise pins of tests/test_oracle_tables.py hold without the reference checkout.
   blocks.json   SHA-256 + shape statistics of the MemoryBlocks the oracle builds under the
                 canonical schedule, and SHA-256 of its Query values on the SplitMix64 point set.
   kats.json     is NOT generated: it holds the known-answer values printed in SURVEY.md
@@ -38,6 +40,15 @@ def tables():
         "nl_2_4": float(r["normalised_lengths"][2, 4]),
     }
     return out
+
+
+def ref_tables_npz(path):
+    import ctypes as C
+    r = O.ref_tables()
+    assert r is not None, "needs oracle/_ref (reference checkout)"
+    scalars = (C.c_ulonglong * 8)()
+    O.ref_tables_lib().ref_scalars(scalars)
+    np.savez_compressed(path, scalars=np.array(list(scalars), np.uint64), **r)
 
 
 CASES = {
@@ -93,4 +104,5 @@ def blocks():
 
 if __name__ == "__main__":
     json.dump(tables(), open(os.path.join(HERE, "tables.json"), "w"), indent=1)
+    ref_tables_npz(os.path.join(HERE, "ref_tables.npz"))
     json.dump(blocks(), open(os.path.join(HERE, "blocks.json"), "w"), indent=1)

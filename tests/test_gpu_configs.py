@@ -949,7 +949,7 @@ def test_bench_two_ranks_sharing_this_gpu():
     env = dict(os.environ, HPSDF_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "400000",
-           "--mesh", "5", "--no-fit-bench", "--no-cpu-baseline", "--no-refined", "--no-sorted-ceiling"]
+           "--full", "--mesh", "5", "--no-fit-bench", "--no-cpu-baseline", "--no-refined", "--no-sorted-ceiling"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -979,7 +979,7 @@ def test_bench_starts_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "400000",
-           "--mesh", "5", "--no-fit-bench", "--no-cpu-baseline", "--no-refined", "--no-sorted-ceiling"]
+           "--full", "--mesh", "5", "--no-fit-bench", "--no-cpu-baseline", "--no-refined", "--no-sorted-ceiling"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1000,7 +1000,7 @@ def test_bench_four_ranks_sharing_this_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--points", "1000000",
-           "--mesh", "7", "--no-fit-bench", "--no-cpu-baseline", "--no-refined", "--no-sorted-ceiling"]
+           "--full", "--mesh", "7", "--no-fit-bench", "--no-cpu-baseline", "--no-refined", "--no-sorted-ceiling"]
     t0 = time.time()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     wall = time.time() - t0
@@ -1016,6 +1016,31 @@ def test_bench_four_ranks_sharing_this_gpu():
     assert isinstance(m["exchanges_per_create_1e-6"], int)
     print("bench.py --gpus 4 on one GPU: %.0f s of wall clock" % wall)
     assert wall < 600  # (the driver's lease: N real GPUs do each of these legs N times faster than four ranks on one)
+
+
+def test_bench_plain_run_dumps_its_last_step(O, tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full): the headline keys only, --steps timed steps, and --dump-outputs writes what the
+    last timed step returned -- here all of it -- which is the oracle's Query on that step's batch, bit for bit."""
+    import json, subprocess, sys
+    from conftest import ROOT
+    n, steps, warmup = 300000, 3, 2
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--points", str(n), "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "Mpts/s" and out["higher_is_better"] is True and out["dtype"] == "f64" and out["create_ms"] > 0
+    for k in ("repeated_batch", "cpu_baseline", "mesh_create", "fit_microbench", "refined_tree", "query_cell_sorted_points"):
+        assert k not in out, k
+    got = np.load(tmp_path / "query_distance.npy")
+    assert got.dtype == np.float64 and got.shape == (n,)
+    last = (warmup + steps - 1) % out["config"]["point_batches"]  # the timed steps walk the batches in turn
+    pts = O.splitmix64_points(n, seed=12345 + 7919 * last)
+    want = O.Tree.create(O.default_config(1e-5), O.union3_field(), 1024).query(pts[::97])
+    assert np.array_equal(bits(got[::97]), bits(want))
 
 
 _NCCL_GATHER = r'''

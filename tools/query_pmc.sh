@@ -12,7 +12,7 @@ for C in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VA
          "TA_TA_BUSY_sum TA_BUSY_avr TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum" \
          "TCP_PENDING_STALL_CYCLES_sum TCP_TA_TCP_STATE_READ_sum TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -- python3 $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/log$i.txt 2>&1
+  rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -- python3 $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/log$i.txt 2>&1
 done
 cd $REPO && python3 - "$OUT" <<'PY'
 import csv, glob, os, sys

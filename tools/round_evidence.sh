@@ -10,7 +10,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 if [ "$PART" = 1 ]; then
   timeout -k 10 700 python -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
   timeout -k 10 500 bash tools/profile.sh $TAG > $O/profile_log.txt 2>&1; tail -5 $O/profile_log.txt
-  timeout -k 10 200 python bench.py > $O/bench.json 2> $O/bench_err.txt; cut -c1-600 $O/bench.json
+  timeout -k 10 200 python bench.py --full > $O/bench.json 2> $O/bench_err.txt; cut -c1-600 $O/bench.json
 elif [ "$PART" = 3 ]; then
   # counters of the fits (-> fit_pmc.json, fit_mfma_pmc.json), Create's kernel timeline, the any-tree query kernels link by link (lab library,
   # built beforehand with build.py --lab), Query on ordered point sets, the default Config()
