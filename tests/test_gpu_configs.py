@@ -458,7 +458,9 @@ def test_needle_meshes_one_answer_on_every_path(H, O, ctx, monkeypatch, seed):
     a face-case point farther outside its triangle than a quarter of the traversal's slack is not taken by a search it could win;
     the closest point of the triangle's boundary takes its place.  So: (1) the O(n) scan kernel, the per-lane traversal and the shared traversal agree BIT FOR BIT, always; (2) wherever
     they differ from the oracle's scan (= the reference's arithmetic), the oracle's value is such an artefact -- below the
-    float64 brute-force distance -- and the product's is that distance."""
+    float64 brute-force distance -- and the product's is that distance.  Its excess over that distance is the f32 routine's
+    conditioning on needles: 2e-4 of the extent on the eight seeds the soaks found first; seed 910968, the most squashed mesh, has
+    a bound of its own, 5e-4, which is not extended to the others."""
     from helpers import fuzz_mesh_case, hard_points, true_distance_f64
     verts, tris, leaf, host, scale, shift = fuzz_mesh_case(seed)
     monkeypatch.setenv("HPSDF_MESH_LEAF_TRIS", str(leaf))
@@ -472,11 +474,12 @@ def test_needle_meshes_one_answer_on_every_path(H, O, ctx, monkeypatch, seed):
     diff = np.nonzero(bits(ref) != bits(scan))[0]
     assert 1 <= len(diff) <= 8, len(diff)  # (the soaks found one point each)
     ext = max(float(np.linalg.norm(verts.max(0) - verts.min(0))), float(np.abs(verts).max()))  # the scale the slack is proportional to
+    band = 5e-4 if seed == 910968 else 2e-4
     for i in diff:
         d = true_distance_f64(verts, tris, pts[i])
         assert abs(ref[i]) < d - 1e-6 * ext, (i, ref[i], d)                   # the reference's value: below the true distance
         # the product's: not below it (beyond the slack), above it by no more than the f32 routine's conditioning on needles
-        assert -1e-5 * ext <= abs(scan[i]) - d <= 5e-4 * max(ext, d), (i, scan[i], d)
+        assert -1e-5 * ext <= abs(scan[i]) - d <= band * max(ext, d), (i, scan[i], d)
     f.close()
 
 
