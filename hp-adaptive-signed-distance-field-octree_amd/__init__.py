@@ -158,6 +158,11 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "hpsdf_function_slice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.c_uint64, C.c_void_p, C.c_void_p]),
+    "hpsdf_surface_case_table": (C.c_int, [C.c_void_p]),
+    "hpsdf_extract_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                        C.c_double, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.c_void_p]),
+    "hpsdf_surface_last_timings": (C.c_int, [C.POINTER(C.c_double)]),
     "hpsdf_build_begin": (C.c_int, [C.POINTER(PodConfig), C.POINTER(BuildOpts), C.POINTER(C.c_void_p)]),
     "hpsdf_build_destroy": (C.c_int, [C.c_void_p]),
     "hpsdf_build_round_select": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -597,6 +602,25 @@ class DeviceTree:
                                          rgb.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p)))
         return rgb, vals
 
+    def extract_surface(self, lo, hi, n, iso=0.0, values=False):
+        """Marching cubes over the lattice of n[a] cubes per axis on [lo, hi] (include/hpsdf.h, hpsdf_extract_surface) ->
+        (verts f64 [V,3], tris u64 [T,3]), plus the lattice values f64 [n2+1, n1+1, n0+1] when values is true."""
+        lo3 = (C.c_double * 3)(*[float(x) for x in lo])
+        hi3 = (C.c_double * 3)(*[float(x) for x in hi])
+        n3 = (C.c_uint32 * 3)(*[int(x) for x in n])
+        vals = np.empty((int(n[2]) + 1, int(n[1]) + 1, int(n[0]) + 1)) if values else None
+        v, t = C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)()
+        nv, nt = C.c_uint64(), C.c_uint64()
+        check(lib().hpsdf_extract_surface(self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), C.byref(v), C.byref(nv), C.byref(t),
+                                          C.byref(nt), vals.ctypes.data_as(C.c_void_p) if values else None))
+        verts, tris = np.zeros((0, 3)), np.zeros((0, 3), np.uint64)
+        if nt.value:
+            verts = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
+            tris = np.ctypeslib.as_array(t, shape=(nt.value, 3)).copy()
+        lib()._libc.free(C.cast(v, C.c_void_p))
+        lib()._libc.free(C.cast(t, C.c_void_p))
+        return (verts, tris, vals) if values else (verts, tris)
+
     def query_device(self, d_xyz_ptr, n, d_out_ptr):
         """Raw device pointers (ints); asynchronous on the context stream."""
         check(lib().hpsdf_query_device(self.ctx.handle, self.handle, C.c_void_p(d_xyz_ptr), n, C.c_void_p(d_out_ptr)))
@@ -952,6 +976,14 @@ class Octree:
         write_bmp(fname + ".bmp", rgb)
         return rgb
 
+    def ExtractSurface(self, view_min, view_max, n, iso=0.0):
+        """Triangle mesh of the level set {Query = iso} over the box [view_min, view_max] with n cubes per axis (an int or three)
+        -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
+        return self._tree.extract_surface(view_min, view_max, n3, iso)
+
     def GetRootAABB(self):
         return self.config.root_min, self.config.root_max
 
@@ -975,6 +1007,30 @@ def write_bmp(path, rgb):
         fh.write(struct.pack("<2sIHHI", b"BM", 14 + 40 + rows.size, 0, 0, 14 + 40))
         fh.write(struct.pack("<IiiHHIIiiII", 40, w, h, 1, 24, 0, 0, 0, 0, 0, 0))
         fh.write(rows.tobytes())
+
+
+def surface_case_table():
+    """hpsdf_surface_case_table: int8 [256, 16], row c = 3 cube-local edges per triangle of case c, then -1 (host only)."""
+    out = np.zeros((256, 16), np.int8)
+    check(lib().hpsdf_surface_case_table(out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def surface_last_timings():
+    """Device milliseconds of the phases of this thread's last extraction: lattice, count, scan, emit, d2h, total."""
+    out = (C.c_double * 6)()
+    check(lib().hpsdf_surface_last_timings(out))
+    return dict(zip(("lattice", "count", "scan", "emit", "d2h", "total"), list(out)))
+
+
+def save_obj(path, verts, tris):
+    """Writes `v` records (each vertex rounded to float32, printed with %.9g: hpsdf_obj_load reads back exactly
+    verts.astype(float32)) and 1-based `f` records."""
+    v = np.asarray(verts, np.float64).reshape(-1, 3).astype(np.float32)
+    t = np.asarray(tris, np.uint64).reshape(-1, 3)
+    with open(path, "w") as fh:
+        fh.write("".join("v %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in v))
+        fh.write("".join("f %d %d %d\n" % (int(a) + 1, int(b) + 1, int(c) + 1) for a, b, c in t))
 
 
 def load_obj(path):

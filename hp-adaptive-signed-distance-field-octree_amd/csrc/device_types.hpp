@@ -53,6 +53,14 @@ struct TreeDev {
     double rootInvSizes[3];  // Octree.cpp:323 (f32 reciprocal widened)
 };
 
+// hpsdf_extract_surface's lattice: np[a] = n[a] + 1 points per axis, nPts = their product (<= 2^30); point (i, j, k) at
+// lo[a] + (f64)i * h[a], index i + np0 (j + np1 k)
+struct SurfaceLattice {
+    double lo[3], h[3];
+    uint32_t n[3], np[3];
+    uint32_t nPts, pad;
+};
+
 enum FieldKind : int32_t { kFieldAnalytic = 0, kFieldSamples = 1, kFieldMesh = 2 };
 
 // Binary BVH node, one 64-byte line: the boxes of BOTH children (so a visit decides about both subtrees from

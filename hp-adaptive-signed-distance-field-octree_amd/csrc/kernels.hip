@@ -2278,6 +2278,25 @@ __global__ __launch_bounds__(256) void slice_points_kernel(double c, float minX,
     }
 }
 
+// The lattice of hpsdf_extract_surface (surface.hip): point L = i + N0 (j + N1 k) at lo + (f64)i h per axis, generated here and sent
+// through queryPoint -- the device code every batched Query path reproduces bit for bit -- so a lattice value is hpsdf_query_device's
+// at that point.  Neighbouring lanes are neighbouring points (x fastest): a wave walks one or two cells' nodes and coefficient lines
+// together.  8 bytes written a point, nothing read but the tree.
+template <int MAXP>
+__global__ __launch_bounds__(256) void lattice_query_kernel(TreeDev t, const DeviceTables* __restrict__ T, SurfaceLattice g,
+                                                            double* __restrict__ out) {
+    __shared__ double sNl[13 * 11];
+    __shared__ double sRec[26];
+    stageQueryTables(T, sNl, sRec);
+    __syncthreads();
+    const uint32_t total = g.nPts;
+    for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < total; p += gridDim.x * 256u) {
+        const uint32_t i = p % g.np[0], r = p / g.np[0], j = r % g.np[1], k = r / g.np[1];
+        const double x = g.lo[0] + (double)i * g.h[0], y = g.lo[1] + (double)j * g.h[1], z = g.lo[2] + (double)k * g.h[2];
+        out[p] = queryPoint<MAXP>(t, x, y, z, sNl, sRec);
+    }
+}
+
 // the CSG wrapper of Octree.cpp:355-400 around an inner field value v
 template <bool CSG>
 __device__ __forceinline__ double applyCsg(const FieldDev& f, double v, double x, double y, double z, const double* sNl,
@@ -3492,6 +3511,18 @@ hipError_t launchSlicePoints(hipStream_t stream, double c, float minX, float min
     if (nSamples == 0) return hipSuccess;
     hipLaunchKernelGGL(slice_points_kernel, dim3(gridFor((size_t)nSamples * nSamples)), dim3(256), 0, stream, c, minX, minY,
                        step, nSamples, dXyz);
+    return hipGetLastError();
+}
+
+hipError_t launchQueryLattice(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const SurfaceLattice& g, double* dOut) {
+    if (g.nPts == 0) return hipSuccess;
+    const dim3 grid(gridFor(g.nPts)), block(256);
+    if (t.maxDegree <= 3)
+        hipLaunchKernelGGL((lattice_query_kernel<3>), grid, block, 0, stream, t, dTables, g, dOut);
+    else if (t.maxDegree <= 5)
+        hipLaunchKernelGGL((lattice_query_kernel<5>), grid, block, 0, stream, t, dTables, g, dOut);
+    else
+        hipLaunchKernelGGL((lattice_query_kernel<12>), grid, block, 0, stream, t, dTables, g, dOut);
     return hipGetLastError();
 }
 

@@ -322,6 +322,42 @@ HPSDF_API int hpsdf_query_ray_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const do
 HPSDF_API int hpsdf_function_slice(hpsdf_ctx* ctx, const hpsdf_tree* t, double c, const float* view_min,
                                    const float* view_max, uint64_t n_samples, uint8_t* rgb, double* values);
 
+/* ---- ExtractSurface: marching cubes over a lattice of Query values (no reference counterpart) ----------------------------------
+ * Lattice: a box lo[a] < hi[a] (finite) and n[a] >= 1 cubes per axis; spacing h[a] = (hi[a] - lo[a]) / n[a]; lattice point (i, j, k)
+ * at x_i = lo[0] + (double)i * h[0] (two roundings, no fused multiply-add), the same for y and z; index L(i,j,k) = i + (n0+1) (j +
+ * (n1+1) k), x fastest.  The value at a lattice point is hpsdf_query_device's at that point on the same context, bit for bit (the
+ * lattice kernel runs Query's own device code).  (n0+1)(n1+1)(n2+1) <= 2^30, and both extreme lattice points (lo and lo + n h) must
+ * pass Query's containment test, so that no value is DBL_MAX -- the root AABB itself passes; otherwise HPSDF_ERR_INVALID_ARGUMENT
+ * and hpsdf_last_error() names the axis.
+ * Classification: a corner is inside iff v < iso (strict; iso finite).  Case of cube (i,j,k): bit dx + 2 dy + 4 dz is set iff
+ * corner (i+dx, j+dy, k+dz) is inside.
+ * Vertices: one per lattice edge whose ends differ in insideness.  An edge runs from its lower point a to b = a + e_axis;
+ * t = (iso - v_a) / (v_b - v_a); the coordinate along the axis is x_a + t (x_b - x_a), the other two are a's exactly; doubles.
+ * Edge id 3 L(a) + axis; vertices are numbered in increasing edge id.
+ * Triangles: ordered by cube Q = i + n0 (j + n1 k), then in case-table order within the cube; indices uint64_t; counter-clockwise
+ * seen from the side where values are >= iso (normals point towards increasing value: outward for an SDF negative inside -- the
+ * winding hpsdf_field_create_mesh expects).
+ * Case table: generated by a face-local rule (csrc/surface_table.hpp).  Cube-local edges: x 0->1, 2->3, 4->5, 6->7 = 0..3;
+ * y 0->2, 1->3, 4->6, 5->7 = 4..7; z 0->4, 1->5, 2->6, 3->7 = 8..11.  On each face the crossing edges are joined by segments: one
+ * around an odd corner (1 or 3 inside), one for 2 adjacent inside corners, two for 2 diagonal inside corners (the inside corners
+ * are separated).  The segments close into loops, each fan-triangulated from its first edge (listed from the smallest) whose
+ * diagonals all leave the cube's faces.  Adjacent cubes agree on every shared face, so the
+ * mesh is watertight and edge-manifold wherever the surface does not leave the box.  At most HPSDF_SURFACE_MAX_TRIS triangles a
+ * case; row c of hpsdf_surface_case_table: 3 cube-local edges a triangle, then -1.  Host-only: needs no device. */
+#define HPSDF_SURFACE_MAX_TRIS 5
+HPSDF_API int hpsdf_surface_case_table(int8_t out[256 * 16]);
+/* Host call, synchronous on the context stream.  *verts (3 doubles a vertex) and *tris (3 indices a triangle) are malloc'd; the
+ * caller frees them.  An empty result is HPSDF_OK with counts 0 and NULL pointers.  values (may be NULL): every lattice value, L
+ * order.  On any error nothing is allocated and the context stays usable; a failed allocation is HPSDF_ERR_OUT_OF_MEMORY.  Device
+ * scratch: 8 bytes a lattice point for the values, ~1.1 more for the crossing bit words, their prefixes and the per-tile triangle
+ * counts (under 10 bytes a point, plus a few KiB for the scans), then the outputs themselves (24 bytes a vertex and a triangle);
+ * all of it is freed before the call returns. */
+HPSDF_API int hpsdf_extract_surface(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3],
+                                    double iso, double** verts, uint64_t* n_verts, uint64_t** tris, uint64_t* n_tris, double* values);
+/* device milliseconds of the phases of this thread's last hpsdf_extract_surface: [0] lattice values, [1] classification and counts,
+ * [2] scans, [3] vertex and triangle output, [4] download, [5] the whole call from its first launch (events on the context stream) */
+HPSDF_API int hpsdf_surface_last_timings(double ms[6]);
+
 /* ---- Create: Octree::Create under the canonical round schedule ---------------
  * (Octree.cpp:312-352, 194-309, 558-659, 804-856, 1007-1093; schedule: DESIGN.md)
  *

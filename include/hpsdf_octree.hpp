@@ -270,6 +270,24 @@ class DeviceField {
     hpsdf_field* f_ = nullptr;
 };
 
+/// Triangle mesh of Octree::ExtractSurface (no reference counterpart): 3 doubles a vertex, 3 zero-based indices a triangle,
+/// counter-clockwise seen from where the field is >= iso (include/hpsdf.h, hpsdf_extract_surface)
+struct SurfaceMesh {
+    std::vector<f64> vertices;
+    std::vector<u64> triangles;
+    /// Wavefront OBJ: `v` records (float32-rounded vertices, %.9g) and 1-based `f` records, what Meshing::ObjParser reads
+    bool WriteObj(const char* path_) const {
+        std::FILE* fh = std::fopen(path_, "w");
+        if (!fh) return false;
+        bool ok = true;
+        for (size_t i = 0; ok && i + 2 < vertices.size(); i += 3)
+            ok = std::fprintf(fh, "v %.9g %.9g %.9g\n", (double)(float)vertices[i], (double)(float)vertices[i + 1], (double)(float)vertices[i + 2]) > 0;
+        for (size_t i = 0; ok && i + 2 < triangles.size(); i += 3)
+            ok = std::fprintf(fh, "f %llu %llu %llu\n", triangles[i] + 1, triangles[i + 1] + 1, triangles[i + 2] + 1) > 0;
+        return std::fclose(fh) == 0 && ok;
+    }
+};
+
 class Octree {
    public:
     typedef std::function<f64(const Eigen::Vector3d& pt_, const u32 threadIdx_)> Func;
@@ -492,6 +510,32 @@ class Octree {
             std::fwrite(row.data(), 1, row.size(), fh);
         }
         std::fclose(fh);
+    }
+
+    /// Marching cubes over resolution_[a] cubes per axis of area_: the level set {Query = iso_} as a closed, consistently wound
+    /// mesh wherever it stays inside area_ (no reference counterpart; include/hpsdf.h, hpsdf_extract_surface)
+    SurfaceMesh ExtractSurface(const Eigen::AlignedBox3f& area_, const Eigen::Vector3i& resolution_, f64 iso_ = 0.0) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        const double lo[3] = {area_.min()(0), area_.min()(1), area_.min()(2)};
+        const double hi[3] = {area_.max()(0), area_.max()(1), area_.max()(2)};
+        uint32_t n[3];
+        for (int a = 0; a < 3; ++a) {
+            if (resolution_(a) < 1) throw Error(HPSDF_ERR_INVALID_ARGUMENT, "resolution must be at least 1 per axis");
+            n[a] = (uint32_t)resolution_(a);
+        }
+        double* v = nullptr;
+        uint64_t* tr = nullptr;
+        uint64_t nv = 0, nt = 0;
+        check(hpsdf_extract_surface(ctx_, t, lo, hi, n, iso_, &v, &nv, &tr, &nt, nullptr));
+        SurfaceMesh m;
+        if (nt) {
+            m.vertices.assign(v, v + 3 * nv);
+            m.triangles.assign(tr, tr + 3 * nt);
+        }
+        std::free(v);
+        std::free(tr);
+        return m;
     }
 
     /// Returns the aabb of the root node   (Octree.h:81)
