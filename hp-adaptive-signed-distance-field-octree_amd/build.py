@@ -16,8 +16,13 @@ HOOKS_LIB = os.path.join(LIBDIR, "libhpsdf_hooks.so")
 HOOK_SOURCES = ["frontier.hip", "capi.cpp"]
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
 
-SOURCES = ["kernels.hip", "frontier.hip", "fit_mfma.hip", "fit_low.hip", "mesh_build.hip", "cg.hip", "continuity_asm.hip", "surface.hip", "tables.cpp", "builder.cpp", "mesh.cpp", "obj.cpp", "continuity.cpp", "host_query.cpp", "capi.cpp"]
+# (the three fit_<kind>.hip are the longest compiles -- they go first)
+SOURCES = ["fit_mesh.hip", "fit_analytic.hip", "fit_samples.hip", "fit.hip", "kernels.hip", "mesh_field.hip", "frontier.hip", "fit_mfma.hip", "fit_low.hip", "mesh_build.hip", "cg.hip", "continuity_asm.hip", "surface.hip", "tables.cpp", "builder.cpp", "mesh.cpp", "obj.cpp", "continuity.cpp", "host_query.cpp", "capi.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))  # every header: an edit to any of them rebuilds every object
+# what a variant build compiles again: the units that hold the code its flags change
+QUERY_SOURCES = ("kernels.hip",)  # the Query kernels (-DHPSDF_QUERY_LAB_BUILD)
+MESH_SOURCES = ("mesh_field.hip", "fit_mesh.hip")  # the units that instantiate mesh_distance.hpp (-DHPSDF_MESH_ABL=n, -DHPSDF_SEED_*, ...)
+SOURCE_GROUPS = {"query": QUERY_SOURCES, "mesh": MESH_SOURCES}
 PUBLIC_HEADERS = ["hpsdf.h", "hpsdf_octree.hpp"]
 
 # -ffp-contract=off: no multiply-add is fused anywhere (bit parity with the x86-64 reference path)
@@ -110,7 +115,7 @@ def build_hooks(cc, objs, verbose=False):
 LAB_LIB = os.path.join(LIBDIR, "libhpsdf_lab.so")
 
 
-def build_variant(name, flags, sources=("kernels.hip",), verbose=False):
+def build_variant(name, flags, sources=QUERY_SOURCES, verbose=False):
     """lib/libhpsdf_<name>.so: the library with `sources` compiled again under extra `flags` -- lab and measurement builds, made ON
     DEMAND only (neither build() nor the tests make or load them; HPSDF_LIBRARY=<name> selects one in the Python loader)."""
     lib = build()
@@ -150,8 +155,8 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     if "--lab" in sys.argv:
         print(build_lab(verbose=True))
-    for a in sys.argv[1:]:  # --variant=name:-DFLAG,-DFLAG2[:source.hip,source2.hip]   (default: kernels.hip compiled again under the flags)
+    for a in sys.argv[1:]:  # --variant=name:-DFLAG,-DFLAG2[:query | mesh | source.hip,source2.hip]   (what is compiled again under the flags; default: query)
         if a.startswith("--variant="):
             name, _, rest = a[len("--variant="):].partition(":")
             fl, _, srcs = rest.partition(":")
-            print(build_variant(name, [f for f in fl.split(",") if f], tuple(x for x in srcs.split(",") if x) or ("kernels.hip",), verbose=True))
+            print(build_variant(name, [f for f in fl.split(",") if f], SOURCE_GROUPS.get(srcs or "query") or tuple(srcs.split(",")), verbose=True))

@@ -569,7 +569,7 @@ int builderCompute(hpsdf_build* b, hpsdf_ctx* ctx, const hpsdf_field* field) {
     // depth, so one launch per (degree, cells-per-thread) run covers them
     bool anyFast = false;
     for (int deg = 0; deg <= kMaxDegree; ++deg) anyFast |= fastDeg(deg);
-    if (!anyFast && nBlocks) {  // every degree in one launch (kernels.hip fit_multi_kernel: longest fits first, all degrees share the chip)
+    if (!anyFast && nBlocks) {  // every degree in one launch (fit_kernels.hpp fit_multi_kernel: longest fits first, all degrees share the chip)
         size_t ldsAll = 0;
         for (int c = 0; c < kClasses; ++c)
             if (classCount[c]) ldsAll = std::max(ldsAll, classShape[c].ldsBytes);

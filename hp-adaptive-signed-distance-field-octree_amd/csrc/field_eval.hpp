@@ -1,5 +1,5 @@
 // Analytic fields on the device: CSG of primitives, evaluated in f64 with the reference's operation order (no fused
-// multiply-add; Eigen's 3-vector reductions as a + (b + c), or (a + b) + c under hpsdf_set_reduction_order(1)).  Shared by kernels.hip and fit_mfma.hip.
+// multiply-add; Eigen's 3-vector reductions as a + (b + c), or (a + b) + c under hpsdf_set_reduction_order(1)).  Shared by kernels.hip (through leaf_eval.hpp), the fit units (field_glue.hpp) and fit_mfma.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,7 +5,7 @@
 //     coeff[cell][r] = N_a N_b N_c * sum_s  Fw[cell][s] * V[s][r],      V[s][r] = P_a(x_i) P_b(x_j) P_c(x_k),
 //     Fw[cell][s] = |cell| * w_i w_j w_k * F(sample s of the cell)                                        (:1028-1056)
 // i.e. a GEMM  C[cells x rows] = Fw[cells x nq^3] * V[nq^3 x rows]  whose A operand is the field itself and whose B
-// operand is a tensor product of three small tables.  fit_kernel (kernels.hip) evaluates it term by term in the
+// operand is a tensor product of three small tables.  fit_kernel (fit_kernels.hpp) evaluates it term by term in the
 // reference's order without fused multiply-adds -- bit-identical to the CPU path, capped at 1/8 of the FP64 peak.  This
 // kernel hands it to v_mfma_f64_16x16x4_f64: one workgroup = one tile of 16 cells, its four waves split the sample
 // dimension four ways; per step of 4 samples every lane evaluates F at ONE (cell, sample) pair -- which is exactly its

@@ -27,7 +27,7 @@
 //                         mirror in pinned host memory tells the host.  Round 0's total (4096 operands that are there when the
 //                         launch starts) it adds up itself
 //   fr_emit_kernel     the round's FitTask / FitBlock lists from the job records (grid: 128 jobs a workgroup, a lane per fit)
-//   mesh_sample_kernel / fit_multi_kernel   (kernels.hip) over device-written ranges: grids are upper bounds.  From the second
+//   mesh_sample_kernel / fit_multi_kernel   (fit_mesh.hip, fit_kernels.hpp) over device-written ranges: grids are upper bounds.  From the second
 //                      round on both are enqueued without waiting for the header: a build that has stopped leaves them nothing to do
 // Larger trees select with a grid: fr_select_kernel (level 0 against the histogram the updates keep), fr_batch_kernel (one
 // workgroup: remaining digits, exact order, classes), fr_tasks_kernel (grid: the lists).
@@ -189,11 +189,11 @@ struct FrDev {
 
 __host__ __device__ inline uint32_t frCoef(int p) { return p == 6 ? 83u : (uint32_t)((p + 1) * (p + 2) * (p + 3) / 6); }
 __host__ __device__ inline int frClass(int degree, bool incr, int depth) { return (2 * degree + (incr ? 1 : 0)) * kFrDepths + depth; }
-__host__ __device__ inline size_t frLds(int degree, int g, int planes) {  // = fitLdsBytes (kernels.hip)
+__host__ __device__ inline size_t frLds(int degree, int g, int planes) {  // = fitLdsBytes (fit.hip)
     const size_t nq = 4 * (size_t)degree + 1;
     return ((size_t)(degree + 1) * nq + 2 * nq + 8 * (size_t)g + (size_t)g * planes * nq * nq) * sizeof(double);
 }
-// workgroup shape of `count` fits of one class: what fitShape (kernels.hip) gives an unweighted, sampled-or-analytic fit
+// workgroup shape of `count` fits of one class: what fitShape (fit.hip) gives an unweighted, sampled-or-analytic fit
 // splitFit: 0 = off, else the lowest degree whose from-scratch fits are split (the context's splitMinDegree)
 constexpr size_t kFrFitLdsCap = 45 * 1024;
 __host__ __device__ inline bool frSplit(int splitFit, int degree, bool incr) { return splitFit > 0 && !incr && degree >= splitFit && degree <= 11; }
@@ -2563,7 +2563,7 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
         d.sampleCap = ws->sampleCap;
         return HPSDF_OK;
     };
-    // a round's fits, from the lists the device wrote (kernels.hip; grids are upper bounds)
+    // a round's fits, from the lists the device wrote (fit_mesh.hip, fit.hip; grids are upper bounds)
     auto launchRoundFits = [&](uint32_t knownMaxDeg, bool splitRound) -> int {
         const int degHi = (int)std::min<uint32_t>(kMaxDegree - 1, knownMaxDeg + 1);
         const uint32_t taskBound = 9u * Kj;
@@ -2578,7 +2578,7 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
         } else if (splitRound) {
             fdr.samples = ws->samples;  // (the exact kernel writes the field values of split fits there)
         }
-        // One launch for every degree of the round (kernels.hip fit_multi_kernel); the matrix-core fit and
+        // One launch for every degree of the round (fit_kernels.hpp fit_multi_kernel); the matrix-core fit and
         // HPSDF_FRONTIER_SPLIT_FITS=1 keep one launch per degree, side by side on three streams.
         static const bool splitFits = std::getenv("HPSDF_FRONTIER_SPLIT_FITS") != nullptr;
         if (!d.fastFit && !splitFits) {

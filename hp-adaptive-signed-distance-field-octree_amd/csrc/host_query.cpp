@@ -4,7 +4,7 @@
 // of 1 M - 8 M points (Source/Tests/HPUnitTests.cpp:64-75, Source/Benchmarks/HPBenchmarks.cpp:105-109).  Through a kernel launch
 // a one-point call is ~15 us whatever the kernel does, so calls of up to kHostQueryPoints points are evaluated here, on the
 // calling thread, from the copy of the block's node array and coefficients the tree handle keeps (hpsdf_tree_upload) -- the
-// same statements in the same order as queryPoint / queryPointWithGradient of kernels.hip (and this file is compiled with
+// same statements in the same order as queryPoint (leaf_eval.hpp) / queryPointWithGradient (kernels.hip) (and this file is compiled with
 // -ffp-contract=off like everything else), so the values are the kernels' bit for bit (tests/test_gpu_parity.py compares them
 // on the edge-point set).  It is not a CPU build of the library: a tree handle only exists on a device context, Create, the
 // fields and every batched call are GPU code, and there is no entry point that works without a GPU.

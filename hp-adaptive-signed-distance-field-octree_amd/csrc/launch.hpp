@@ -1,4 +1,4 @@
-// Host-side launch wrappers of kernels.hip.
+// Host-side launch wrappers of every .hip unit, grouped by the file that defines them.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -6,16 +6,37 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 
 #include "device_types.hpp"
 
 namespace hpsdf {
 
-constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
-constexpr int kFitBlockThreads = 256;
+// ---- Query (kernels.hip)
 constexpr unsigned kQueryMaxGrid = 256 * 8 * 4;  // workgroups of one Query launch (grid-stride beyond)
 constexpr size_t kQueryFewPoints = 256;  // up to here Query is one launch of query_few_kernel (one lane per point)
-
+// grid of the kernels that stride over points in workgroups of 256 (Query, field_kernel)
+inline unsigned gridFor(size_t n) {
+    size_t blocks = (n + 255) / 256;
+    static const size_t capEnv = [] { const char* e = std::getenv("HPSDF_QUERY_GRID"); return e ? (size_t)std::max(1, std::atoi(e)) : (size_t)0; }();  // tuning knob
+    const size_t cap = capEnv ? capEnv : kQueryMaxGrid;  // grid-stride beyond this (the headline kernel: 512 ... 39 063 workgroups for 10 M points measured, flat from 4096 up)
+    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+hipError_t launchQuery(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
+                       double* dOut, double* dGrad, bool allInline, uint32_t* dDeferCount, uint32_t* dDeferIdx);
+hipError_t launchQueryRay(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dOrigins,
+                          const double* dDirs, const double* dTMax, size_t n, uint8_t* dHit, double* dT);
+// hpsdf_extract_surface's lattice: lattice point L's Query value into dOut[L] (kernels.hip, lattice_query_kernel)
+hipError_t launchQueryLattice(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const SurfaceLattice& g, double* dOut);
+hipError_t launchSlicePoints(hipStream_t stream, double c, float minX, float minY, float step, uint32_t nSamples,
+                             double* dXyz);
+// weighted builds: |mean FApprox| of every fit of the blocks (fit_weight_kernel)
+hipError_t launchFitWeight(hipStream_t stream, const FitBlock* dBlocks, uint32_t nBlocks, size_t ldsBytes, const FitTask* dTasks,
+                           const double* dArena, double* dMeans, const DeviceTables* dTables, const uint32_t* dCount = nullptr);
+// ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
+constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
+constexpr int kFitBlockThreads = 256;
+constexpr int kFitThreads = 256;  // threads of a fit workgroup (fit_kernels.hpp, fit_weight_kernel)
 constexpr size_t kFitChunkLdsBytes = 40 * 1024;  // sample planes staged per chunk (keeps >= 3 workgroups per CU)
 size_t fitLdsBytes(int degree, int nTasks, int planes);
 struct FitShape {
@@ -26,16 +47,21 @@ struct FitShape {
 };
 // latencyBound: the field is a BVH traversal (mesh): one cell per workgroup, occupancy hides the gathers
 FitShape fitShape(int degree, int nrows, uint32_t count, bool weighted, bool latencyBound = false);
-
-
 hipError_t launchFit(hipStream_t stream, int degree, int cellsPerThread, const FitBlock* dBlocks, uint32_t nBlocks, size_t ldsBytes,
                      const FitTask* dTasks, double* dArena, double* dErrs, double* dMirror,  // dMirror: a second destination of the rows (host memory the device can write), or nullptr
                      const DeviceTables* dTables, const FieldDev& field, const RootMap& rm, const uint32_t* dRange = nullptr);
 hipError_t launchFitMulti(hipStream_t stream, const FitBlock* dBlocks, uint32_t maxBlocks, size_t ldsBytes, const FitTask* dTasks,
                           double* dArena, double* dErrs, const DeviceTables* dTables, const FieldDev& field, const RootMap& rm,
                           const uint32_t* dCount);
-hipError_t launchFitWeight(hipStream_t stream, const FitBlock* dBlocks, uint32_t nBlocks, size_t ldsBytes, const FitTask* dTasks,
-                           const double* dArena, double* dMeans, const DeviceTables* dTables, const uint32_t* dCount = nullptr);
+hipError_t launchFieldEval(hipStream_t stream, const FieldDev& f, const DeviceTables* dTables, const double* dXyz,
+                           size_t n, double* dOut);
+hipError_t launchPack(hipStream_t stream, const PackItem* dItems, uint32_t nItems, const double* dArena, double* dOut);
+// mesh fields (fit_mesh.hip): F at every sample of nTasks fits of one degree -> dSamples[FitTask::sampleOff + sample]
+hipError_t launchMeshSample(hipStream_t stream, const FitTask* dTasks, uint32_t nTasks, int degree, const DeviceTables* dTables,
+                            const FieldDev& field, const RootMap& rm, double* dSamples);
+hipError_t launchMeshSampleRange(hipStream_t stream, const FitTask* dTasks, const uint32_t* dRange, uint32_t maxTasks, int degree,
+                                 const DeviceTables* dTables, const FieldDev& field, const RootMap& rm, double* dSamples);
+// ---- the fits on the matrix cores (fit_mfma.hip, fit_low.hip)
 // opt-in fast fit of degrees 4..11 on the matrix cores (fit_mfma.hip): blocks of at most 16 fits, NOT bit-identical to launchFit
 constexpr int kMfmaCells = 16;
 bool fitMfmaSupports(int degree, const FieldDev& field);
@@ -50,25 +76,9 @@ hipError_t launchFitLow(hipStream_t stream, int degree, const FitTask* dTasks, c
                         uint32_t maxTasks, double* dArena, const DeviceTables* dTables, const double* dSamples);  // fit_low.hip
 hipError_t launchFitMfmaLow(hipStream_t stream, int degree, const FitTask* dTasks, const uint32_t* dRange, uint32_t first, uint32_t count,
                             uint32_t maxTasks, double* dArena, const DeviceTables* dTables, const double* dSamples, const RootMap& rm, int leftAssoc);
-hipError_t launchQuery(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
-                       double* dOut, double* dGrad, bool allInline, uint32_t* dDeferCount, uint32_t* dDeferIdx);
-hipError_t launchQueryRay(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dOrigins,
-                          const double* dDirs, const double* dTMax, size_t n, uint8_t* dHit, double* dT);
-// hpsdf_extract_surface's lattice: lattice point L's Query value into dOut[L] (kernels.hip, lattice_query_kernel)
-hipError_t launchQueryLattice(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const SurfaceLattice& g, double* dOut);
-hipError_t launchSlicePoints(hipStream_t stream, double c, float minX, float minY, float step, uint32_t nSamples,
-                             double* dXyz);
-hipError_t launchFieldEval(hipStream_t stream, const FieldDev& f, const DeviceTables* dTables, const double* dXyz,
-                           size_t n, double* dOut);
+// ---- mesh fields (mesh_field.hip)
 // mesh field, linear scan over all triangles (no BVH): Mesh::SignedDistanceAtPt(pt), Mesh.cpp:42-51,134-159
 hipError_t launchMeshEvalWave(hipStream_t stream, const FieldDev& f, const double* dXyz, size_t n, double* dOut);
-// rocPRIM's radix sort of (key, value) pairs on the low `bits` bits (mesh_build.hip); tmp == nullptr: tmpBytes receives the scratch size
-hipError_t sortPairsU32(hipStream_t stream, void* tmp, size_t& tmpBytes, const uint32_t* keys, uint32_t* keysOut, const uint32_t* vals, uint32_t* valsOut,
-                        size_t n, unsigned bits);
-// the library's private stream-ordered pool of a device (mesh_build.hip; never the application's default pool), and its trim
-hipMemPool_t meshPool(int dev);
-void meshPoolTrim(int dev);
-
 // a few points of a plain mesh field on the calling thread; hm: HOST copies of the field's arrays
 void meshEvalHostPoints(const MeshDev& hm, const double* xyz, size_t n, double* out);
 // dKeys: n x 8 bytes of DEVICE memory for the per-point (distance, triangle) keys, or nullptr when dOut itself is device memory
@@ -79,11 +89,13 @@ constexpr int kTriPreFloats = 12;     // MeshDev::triPre: g hu | unit normal hv 
 // dSlotTri: which triangle sits in leaf slot s (nullptr: slot s = triangle s); either output may be nullptr (skipped)
 hipError_t launchMeshTriPos(hipStream_t stream, const float* dVerts, const uint32_t* dTris, uint64_t nTris, float* dTriPos,
                             const uint32_t* dSlotTri, float* dTriPre);
-// mesh fields: F at every sample of nTasks fits of one degree -> dSamples[FitTask::sampleOff + sample]
-hipError_t launchMeshSample(hipStream_t stream, const FitTask* dTasks, uint32_t nTasks, int degree, const DeviceTables* dTables,
-                            const FieldDev& field, const RootMap& rm, double* dSamples);
-hipError_t launchMeshSampleRange(hipStream_t stream, const FitTask* dTasks, const uint32_t* dRange, uint32_t maxTasks, int degree,
-                                 const DeviceTables* dTables, const FieldDev& field, const RootMap& rm, double* dSamples);
+// ---- mesh preparation (mesh_build.hip)
+// rocPRIM's radix sort of (key, value) pairs on the low `bits` bits (mesh_build.hip); tmp == nullptr: tmpBytes receives the scratch size
+hipError_t sortPairsU32(hipStream_t stream, void* tmp, size_t& tmpBytes, const uint32_t* keys, uint32_t* keysOut, const uint32_t* vals, uint32_t* valsOut,
+                        size_t n, unsigned bits);
+// the library's private stream-ordered pool of a device (mesh_build.hip; never the application's default pool), and its trim
+hipMemPool_t meshPool(int dev);
+void meshPoolTrim(int dev);
 // ---- continuity solve on the device (cg.hip); the arithmetic is continuity.cpp's
 constexpr uint64_t kCgChunk = 256;  // dot products are summed chunk by chunk (one workgroup's rows), then over the chunks
 // The canonical sum of one chunk, e[0..count) with count <= 256 (missing elements count as +0.0): lane l of 64 adds
@@ -145,6 +157,5 @@ struct CgDev {
 hipError_t launchCgStart(hipStream_t stream, const CgDev& d);   // setup, jump energy before, first residual, threshold
 hipError_t launchCgIterations(hipStream_t stream, const CgDev& d, int firstIteration, int iterations, uint32_t stamp = 0);
 hipError_t launchCgFinish(hipStream_t stream, const CgDev& d);  // jump energy after
-hipError_t launchPack(hipStream_t stream, const PackItem* dItems, uint32_t nItems, const double* dArena, double* dOut);
 
 }  // namespace hpsdf

@@ -169,7 +169,7 @@ struct hpsdf_field {
     uint32_t nTris = 0, nVerts = 0, nBvhNodes = 0;
     unsigned long long* dStats = nullptr;  // 4 counters, only under HPSDF_MESH_STATS=1
     // host copies of the arrays above, made by the first call of one or two points (hpsdf_field_eval_host, n <= kHostMeshPoints): such calls
-    // are answered on the calling thread (kernels.hip, meshEvalHostPoints) -- what Mesh::SignedDistanceAtPt(pt, bvh) inside a user's
+    // are answered on the calling thread (mesh_field.hip, meshEvalHostPoints) -- what Mesh::SignedDistanceAtPt(pt, bvh) inside a user's
     // SDF lambda costs decides whether code written against the reference is usable as it is
     struct HostMirror {
         std::vector<float> verts, triPos, triPre;

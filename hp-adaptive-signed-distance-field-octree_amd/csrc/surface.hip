@@ -197,7 +197,7 @@ __global__ __launch_bounds__(kSurfBlock) void surf_tri_kernel(const double* __re
 
 size_t alignUp(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// the f32 containment test of queryPoint (kernels.hip, Octree.cpp:665-668) on one coordinate
+// the f32 containment test of queryPoint (leaf_eval.hpp, Octree.cpp:665-668) on one coordinate
 bool inRoot(const TreeDev& t, int a, double x) {
     const float f = (float)((x - t.rootCentre[a]) * t.rootInvSizes[a]);
     return f >= -0.5f && f <= 0.5f;

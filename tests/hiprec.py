@@ -35,7 +35,7 @@ terms are products of two relative errors each below (n + 200) u < 2e-11, so eve
    (i)   L_a by the three-term recurrence L_j = rec[j][0] x L_{j-1} - rec[j][1] L_{j-2} in float64: |dL_j| <= j^2 u on [-1, 1]
          (the absolute model; tests/test_hiprec_cpu.py checks it on every node of every rule the fits use).  Its contribution
          to row r is u N S sum_s |w_i w_j w_k F_s| (a^2 |L_b L_c| + b^2 |L_a L_c| + c^2 |L_a L_b|) =: u R_r.
-   (ii)  at most K_MUL = 12 multiplicative roundings on each term.  The exact kernel (kernels.hip, as hp_oracle.c:420-441):
+   (ii)  at most K_MUL = 12 multiplicative roundings on each term.  The exact kernel (fit_kernels.hpp, as hp_oracle.c:420-441):
          Lp: 5 (the first *= of 1.0 is exact), S = prod3(scale): 2, wprod: 2, S * wprod: 1, * F: 1, Lp * FaabSample: 1 -> 12.
          The split kernel (fit_low.hip:65-143): A = w P: 1 per axis (3), the three contractions are fused multiply-adds (their
          products exact), then ((S N_a)(N_b N_c)) s: 4, plus S: 2 -> 9.  The matrix-core kernels (fit_mfma.hip) form the same
@@ -200,7 +200,7 @@ def fit_reference(spec, root_min, root_max, bmin, bmax, degree, depth, left=Fals
     rmin, rmax = np.asarray(root_min, np.float32), np.asarray(root_max, np.float32)
     rb = (rmax - rmin).astype(np.float64)
     rc = ((rmin + rmax) / np.float32(2.0)).astype(np.float64)
-    # :1039 and :327 (kernels.hip: w = u * bounds + centre): float64, unfused
+    # :1039 and :327 (fit_kernels.hpp: w = u * bounds + centre): float64, unfused
     wx = [(x[None, :] * scale[:, a:a + 1] + centre[:, a:a + 1]) * rb[a] + rc[a] for a in range(3)]
     X = np.broadcast_to(wx[0][:, :, None, None], (C, nq, nq, nq))
     Y = np.broadcast_to(wx[1][:, None, :, None], (C, nq, nq, nq))

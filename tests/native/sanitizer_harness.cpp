@@ -21,7 +21,7 @@ int fail(int code, const std::string& msg) {
 int hipFail(hipError_t, const char*) { return HPSDF_ERR_HIP; }
 const hpsdf_field* innermost(const hpsdf_field* f) { return f; }
 int makeFieldDev(const hpsdf_ctx*, const hpsdf_field*, const double*, FieldDev*) { return HPSDF_ERR_UNSUPPORTED; }
-// the GPU legs are not exercised here (no device): link-time stand-ins for the launch wrappers of kernels.hip
+// the GPU legs are not exercised here (no device): link-time stand-ins for the launch wrappers of the .hip units (launch.hpp)
 size_t fitLdsBytes(int, int, int) { return 0; }
 FitShape fitShape(int, int, uint32_t, bool, bool) { return FitShape{1, 1, 1, 0}; }
 hipError_t launchFit(hipStream_t, int, int, const FitBlock*, uint32_t, size_t, const FitTask*, double*, double*, double*,

@@ -431,7 +431,7 @@ def _hard_points(O, verts, tris, seed):
 
 @pytest.mark.parametrize("host_build", [False, True])
 def test_mesh_lower_bound_filter_keeps_the_scan_winner(H, O, ctx, monkeypatch, host_build):
-    """Leaves of several triangles and the plane-and-circle lower bound in front of the closest-point test (kernels.hip,
+    """Leaves of several triangles and the plane-and-circle lower bound in front of the closest-point test (mesh_distance.hpp,
     triLowerBound2) only skip work: per-lane traversal, the sampler's shared traversal and the O(n) scan return the same
     bits -- on thin triangles, slivers, meshes far from the origin, points on the surface and in the medial region, with
     the device-built LBVH and with the host-built tree."""
@@ -454,7 +454,7 @@ def test_needle_meshes_one_answer_on_every_path(H, O, ctx, monkeypatch, seed):
     disagree (spheres and tori squashed up to 1000 : 1: every triangle a needle).  The reference's closest-point routine
     (Utility.cpp:5-97) forms its face-case point from barycentric quotients and returns it even when the weights put it outside
     the triangle -- its absolute 1e-6 guards let that happen beside short edges -- i.e. a distance BELOW the triangle's, which a
-    search sees or not depending on what it prunes (BVH.cpp:263-342 would too).  The product's rule (kernels.hip, closestSimplex):
+    search sees or not depending on what it prunes (BVH.cpp:263-342 would too).  The product's rule (mesh_distance.hpp, closestSimplex):
     a face-case point farther outside its triangle than a quarter of the traversal's slack is not taken by a search it could win;
     the closest point of the triangle's boundary takes its place.  So: (1) the O(n) scan kernel, the per-lane traversal and the shared traversal agree BIT FOR BIT, always; (2) wherever
     they differ from the oracle's scan (= the reference's arithmetic), the oracle's value is such an artefact -- below the

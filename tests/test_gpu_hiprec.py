@@ -18,7 +18,7 @@ WORST = {}
 
 
 # ---------------------------------------------------------------------------------------------------------------- shapes
-# Restated from csrc/launch.hpp, csrc/kernels.hip (fitShape) and csrc/fit_low.hip (LowShape) so that the counts below are
+# Restated from csrc/launch.hpp, csrc/fit.hip (fitShape) and csrc/fit_low.hip (LowShape) so that the counts below are
 # chosen from the kernels' tilings, not guessed.
 K_FIT_THREADS, K_FIT_MAX_LDS, K_MFMA_CELLS = 256, 60 * 1024, 16
 

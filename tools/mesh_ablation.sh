@@ -9,7 +9,7 @@ if [ "${1:-}" = build ]; then
     python3 hp-adaptive-signed-distance-field-octree_amd/build.py > /dev/null || exit 1
     pids=""
     for v in $VARIANTS; do
-        python3 hp-adaptive-signed-distance-field-octree_amd/build.py --variant=$v > /dev/null &
+        python3 hp-adaptive-signed-distance-field-octree_amd/build.py --variant=$v:mesh > /dev/null &
         pids="$pids $!"
         if [ $(echo $pids | wc -w) -ge 4 ]; then wait $pids; pids=""; fi
     done

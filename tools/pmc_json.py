@@ -17,8 +17,10 @@ def source_sha16(files):
     return h.hexdigest()[:16]
 
 
-MESH_FILES = ["kernels.hip", "device_types.hpp", "acosf_host_libm.hpp"]
-FIT_FILES = ["kernels.hip", "fit_low.hip", "field_eval.hpp", "device_types.hpp"]
+# the files that hold each record's kernels and what they inline (mesh_sample_kernel: fit_mesh.hip; the fit: fit_kernels.hpp and its units)
+MESH_FILES = ["fit_mesh.hip", "fit_kernels.hpp", "mesh_distance.hpp", "device_types.hpp", "acosf_host_libm.hpp"]
+FIT_FILES = ["fit_kernels.hpp", "fit.hip", "fit_analytic.hip", "fit_samples.hip", "fit_mesh.hip", "fit_low.hip", "field_glue.hpp", "field_eval.hpp", "leaf_eval.hpp",
+             "mesh_distance.hpp", "device_types.hpp"]
 MFMA_FILES = ["fit_mfma.hip", "field_eval.hpp", "device_types.hpp"]
 
 
