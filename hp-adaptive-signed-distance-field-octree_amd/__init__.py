@@ -163,6 +163,13 @@ _SIGNATURES = {
                                         C.c_double, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_uint64),
                                         C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.c_void_p]),
     "hpsdf_surface_last_timings": (C.c_int, [C.POINTER(C.c_double)]),
+    "hpsdf_extract_surface_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                               C.c_double, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.c_void_p]),
+    "hpsdf_surface_classify_host": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                              C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "hpsdf_surface_classify_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                                C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
     "hpsdf_build_begin": (C.c_int, [C.POINTER(PodConfig), C.POINTER(BuildOpts), C.POINTER(C.c_void_p)]),
     "hpsdf_build_destroy": (C.c_int, [C.c_void_p]),
     "hpsdf_build_round_select": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -621,6 +628,36 @@ class DeviceTree:
         lib()._libc.free(C.cast(t, C.c_void_p))
         return (verts, tris, vals) if values else (verts, tris)
 
+    def extract_surface_sparse(self, lo, hi, n, iso=0.0, stats=False):
+        """extract_surface's mesh, bit for bit, evaluated only in the blocks of 8^3 cubes the tree cannot rule out (include/hpsdf.h,
+        hpsdf_extract_surface_sparse): up to 2^40 lattice points, device memory proportional to the surface -> (verts f64 [V,3],
+        tris u64 [T,3]), plus the call's statistics as a dict when stats is true."""
+        lo3, hi3, n3 = _lattice_args(lo, hi, n)
+        st = SurfaceSparseStats()
+        v, t = C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)()
+        nv, nt = C.c_uint64(), C.c_uint64()
+        check(lib().hpsdf_extract_surface_sparse(self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), C.byref(v), C.byref(nv), C.byref(t),
+                                                 C.byref(nt), C.byref(st)))
+        verts, tris = np.zeros((0, 3)), np.zeros((0, 3), np.uint64)
+        if nt.value:
+            verts = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
+            tris = np.ctypeslib.as_array(t, shape=(nt.value, 3)).copy()
+        lib()._libc.free(C.cast(v, C.c_void_p))
+        lib()._libc.free(C.cast(t, C.c_void_p))
+        if not stats:
+            return verts, tris
+        return verts, tris, {k: getattr(st, k) for k, _ in SurfaceSparseStats._fields_ if k != "reserved"}
+
+    def classify_surface_blocks(self, lo, hi, n, iso=0.0, first_block=0, count=None):
+        """The classification kernel's class byte per block (0 evaluate, 1 all >= iso, 2 all < iso) for blocks [first_block,
+        first_block + count), default all of them, x fastest -> u8 [count]."""
+        lo3, hi3, n3 = _lattice_args(lo, hi, n)
+        count = surface_block_count(n) - int(first_block) if count is None else int(count)
+        out = np.zeros(max(count, 0), np.uint8)
+        check(lib().hpsdf_surface_classify_device(self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), int(first_block), count,
+                                                  out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def query_device(self, d_xyz_ptr, n, d_out_ptr):
         """Raw device pointers (ints); asynchronous on the context stream."""
         check(lib().hpsdf_query_device(self.ctx.handle, self.handle, C.c_void_p(d_xyz_ptr), n, C.c_void_p(d_out_ptr)))
@@ -976,12 +1013,15 @@ class Octree:
         write_bmp(fname + ".bmp", rgb)
         return rgb
 
-    def ExtractSurface(self, view_min, view_max, n, iso=0.0):
+    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False):
         """Triangle mesh of the level set {Query = iso} over the box [view_min, view_max] with n cubes per axis (an int or three)
-        -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice."""
+        -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice.  sparse: the same arrays through
+        DeviceTree.extract_surface_sparse (lattices up to 2^40 points)."""
         if self._tree is None:
             raise HpsdfError(6, "Query on an empty octree")
         n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
+        if sparse:
+            return self._tree.extract_surface_sparse(view_min, view_max, n3, iso)
         return self._tree.extract_surface(view_min, view_max, n3, iso)
 
     def GetRootAABB(self):
@@ -1013,6 +1053,35 @@ def surface_case_table():
     """hpsdf_surface_case_table: int8 [256, 16], row c = 3 cube-local edges per triangle of case c, then -1 (host only)."""
     out = np.zeros((256, 16), np.int8)
     check(lib().hpsdf_surface_case_table(out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class SurfaceSparseStats(C.Structure):  # hpsdf_surface_sparse_stats, 96 bytes
+    _fields_ = [("blocks", C.c_uint64), ("active_blocks", C.c_uint64), ("leaves_visited", C.c_uint64),
+                ("classify_ms", C.c_double), ("count_ms", C.c_double), ("scan_ms", C.c_double), ("emit_ms", C.c_double),
+                ("sort_ms", C.c_double), ("download_ms", C.c_double), ("total_ms", C.c_double),
+                ("peak_scratch_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+SURFACE_BLOCK = 8  # HPSDF_SURFACE_BLOCK
+
+
+def _lattice_args(lo, hi, n):
+    return ((C.c_double * 3)(*[float(x) for x in lo]), (C.c_double * 3)(*[float(x) for x in hi]), (C.c_uint32 * 3)(*[int(x) for x in n]))
+
+
+def surface_block_count(n):
+    """Blocks of the lattice of n[a] cubes per axis: the product of ceil(n[a] / 8)."""
+    return int(np.prod([(int(x) + SURFACE_BLOCK - 1) // SURFACE_BLOCK for x in n], dtype=object))
+
+
+def surface_classify_host(block, lo, hi, n, iso=0.0, first_block=0, count=None):
+    """hpsdf_surface_classify_host: DeviceTree.classify_surface_blocks' bytes from a serialised block on the calling thread (no device)."""
+    lo3, hi3, n3 = _lattice_args(lo, hi, n)
+    count = surface_block_count(n) - int(first_block) if count is None else int(count)
+    out = np.zeros(max(count, 0), np.uint8)
+    buf = bytes(block)
+    check(lib().hpsdf_surface_classify_host(buf, len(buf), lo3, hi3, n3, float(iso), int(first_block), count, out.ctypes.data_as(C.c_void_p)))
     return out
 
 

@@ -1,0 +1,927 @@
+// hpsdf_extract_surface_sparse: hpsdf_extract_surface's mesh, bit for bit, evaluated only in the blocks of 8^3 cubes the tree cannot
+// rule out (include/hpsdf.h states the blocks, the classes, the bound and the derivation of its slack).
+//
+//   1. sparse_depth_kernel / sparse_consts_kernel: per leaf G_x, G_y, G_z, S (leafBound) -- the depth of a node is not in the 8-byte
+//      mirror, one workgroup hands it down level by level;
+//   2. sparse_classify_kernel: one lane per block walks the tree with the block's two extreme lattice points (classifyBlock: the very
+//      function hpsdf_surface_classify_host runs on the calling thread, so both give the same bytes);
+//   3. rocPRIM reduce + select: the class-0 blocks in block order;
+//   4. sparse_block_kernel<COUNT>: one workgroup per active block -- its <= 9^3 values through Query's queryPoint into LDS, ballots of
+//      the crossing edges it owns and its cubes' triangle counts from the case table;  rocPRIM exclusive scans of both;
+//   5. sparse_block_kernel<EMIT>: the values again (5.8 KB a block is not stored), then vertex records (edge id, xyz) and triangle
+//      records (key 8 Q + index in the cube, three edge ids) at the prefixes;
+//   6. rocPRIM radix sorts of (edge id, record) and (key, record); sparse_gather_kernel puts the vertices in edge-id order and
+//      sparse_renumber_kernel replaces a triangle's edge ids by their ranks among the sorted vertex keys (binary search): the dense
+//      call's numbering, with no neighbour logic.
+// No atomics on anything that reaches the output (one counter of visited leaves for the statistics).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "block_check.hpp"
+#include "device_types.hpp"
+#include "leaf_eval.hpp"
+#include "runtime.hpp"
+#include "surface_table.hpp"
+#include "tables.hpp"
+#include "hpsdf.h"
+
+namespace hpsdf {
+
+namespace {
+
+constexpr uint32_t kB = HPSDF_SURFACE_BLOCK;  // cubes per axis of a block
+constexpr uint32_t kP = kB + 1;               // points per axis of its closed range
+constexpr uint32_t kBlockPts = kP * kP * kP;  // 729
+constexpr uint32_t kBlockCubes = kB * kB * kB;
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kEdgeRounds = (3 * kBlockPts + kThreads - 1) / kThreads;  // 9
+constexpr uint32_t kCubeRounds = kBlockCubes / kThreads;                     // 2
+constexpr int kLevels = HPSDF_TREE_MAX_DEPTH + 2;
+constexpr double kClip = 1.0 + 1.0 / 16384.0;  // 1 + E, E = 2^-14 (include/hpsdf.h)
+
+struct SparseLattice {
+    double lo[3], h[3];
+    uint32_t n[3], nb[3];
+    uint64_t np[3];  // points per axis
+    uint64_t nBlocks;
+};
+
+// What the walk reads of a tree: the 8-byte records, the line-aligned coefficients, 4 constants per node, the root map.
+struct ClsTree {
+    const NodeRec* nodes;
+    const double* coeffs;
+    const double* consts;  // per node: G_x, G_y, G_z, S (zeros for interior nodes)
+    double rootCentre[3], rootInvSizes[3];
+};
+
+// G_a and S of one leaf (include/hpsdf.h): sums of non-negative terms, in row order
+__host__ __device__ inline void leafBound(const double* __restrict__ c, uint32_t count, int depth, const double* __restrict__ nl,
+                                          const uint8_t (*__restrict__ bidx)[4], double* __restrict__ out) {
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0, s = 0.0;
+    for (uint32_t r = 0; r < count; ++r) {
+        const uint32_t k0 = bidx[r][0], k1 = bidx[r][1], k2 = bidx[r][2];
+        double w = fabs(c[r]);
+        w = w * nl[k0 * 11 + depth];
+        w = w * nl[k1 * 11 + depth];
+        w = w * nl[k2 * 11 + depth];
+        s = s + w;
+        g0 = g0 + w * (double)(k0 * (k0 + 1u) / 2u);
+        g1 = g1 + w * (double)(k1 * (k1 + 1u) / 2u);
+        g2 = g2 + w * (double)(k2 * (k2 + 1u) / 2u);
+    }
+    out[0] = g0, out[1] = g1, out[2] = g2, out[3] = s;
+}
+
+// children a walk with the range [pl, ph] must visit below a node centred at c: per axis the lower half if pl < c, the upper if ph >= c
+__host__ __device__ inline uint32_t childMask(const double (&pl)[3], const double (&ph)[3], const double* c) {
+    uint32_t m = 0xFFu;
+    for (int a = 0; a < 3; ++a) {
+        const uint32_t upper = a == 0 ? 0xAAu : (a == 1 ? 0xCCu : 0xF0u);  // children whose bit a is set
+        if (!(pl[a] < c[a])) m &= upper;
+        if (!(ph[a] >= c[a])) m &= ~upper;
+    }
+    return m;
+}
+
+// The class of block b (include/hpsdf.h).  eval(c, degree, ux, uy, uz, depth): the leaf's polynomial as Query evaluates it.
+template <class Eval>
+__host__ __device__ inline uint8_t classifyBlock(const ClsTree& t, const SparseLattice& g, double iso, uint64_t b, const Eval& eval,
+                                                 uint32_t& visited) {
+    visited = 0;
+    const uint64_t r = b / g.nb[0];
+    const uint32_t bi[3] = {(uint32_t)(b - r * g.nb[0]), (uint32_t)(r % g.nb[1]), (uint32_t)(r / g.nb[1])};
+    double pl[3], ph[3];
+    for (int a = 0; a < 3; ++a) {
+        const uint32_t i0 = kB * bi[a], i1 = i0 + kB < g.n[a] ? i0 + kB : g.n[a];
+        const double xl = g.lo[a] + (double)i0 * g.h[a], xh = g.lo[a] + (double)i1 * g.h[a];
+        pl[a] = (xl - t.rootCentre[a]) * t.rootInvSizes[a];
+        ph[a] = (xh - t.rootCentre[a]) * t.rootInvSizes[a];
+        const float fl = (float)pl[a], fh = (float)ph[a];
+        if (!(fl >= -0.5f && fl <= 0.5f && fh >= -0.5f && fh <= 0.5f)) return 0;  // a corner fails Query's containment test
+        if (!(pl[a] <= ph[a])) return 0;
+    }
+    if (t.nodes[0].b != kInteriorTag) return 0;
+    uint32_t first[kLevels];
+    uint32_t mask[kLevels];
+    double cen[kLevels][3];
+    int depth = 0, sign = 0;
+    first[0] = t.nodes[0].a;
+    cen[0][0] = cen[0][1] = cen[0][2] = 0.0;
+    mask[0] = childMask(pl, ph, cen[0]);
+    while (depth >= 0) {
+        const uint32_t m = mask[depth];
+        if (m == 0) {
+            --depth;
+            continue;
+        }
+        const uint32_t ch = (uint32_t)__builtin_ctz(m);
+        mask[depth] = m & (m - 1u);
+        const double q = 0.25 / (double)(1u << depth);  // half the child's size: exact
+        double cc[3];
+        for (int a = 0; a < 3; ++a) cc[a] = (ch >> a) & 1u ? cen[depth][a] + q : cen[depth][a] - q;
+        const uint32_t node = first[depth] + ch;
+        const NodeRec rec = t.nodes[node];
+        if (rec.b == kInteriorTag) {
+            if (depth + 1 >= kLevels) return 0;
+            ++depth;
+            first[depth] = rec.a;
+            cen[depth][0] = cc[0], cen[depth][1] = cc[1], cen[depth][2] = cc[2];
+            mask[depth] = childMask(pl, ph, cc);
+            continue;
+        }
+        const int ld = depth + 1;  // the leaf's depth
+        if (++visited > (uint32_t)HPSDF_SURFACE_MAX_LEAVES || ld > HPSDF_TREE_MAX_DEPTH) return 0;
+        const double s = (double)(2 << ld);
+        double uc[3], rho[3];
+        bool reached = true;
+        for (int a = 0; a < 3; ++a) {
+            double ua = (pl[a] - cc[a]) * s, ub = (ph[a] - cc[a]) * s;  // Octree.cpp:862 on the two extreme points
+            ua = ua < -kClip ? -kClip : ua;
+            ub = ub > kClip ? kClip : ub;
+            if (!(ua <= ub)) reached = false;  // no point of the block lies in this leaf
+            uc[a] = 0.5 * (ua + ub);
+            rho[a] = 0.5 * (ub - ua);
+        }
+        if (!reached) continue;
+        const double* K = t.consts + 4 * (size_t)node;
+        const double bound = HPSDF_SURFACE_SLACK * ((rho[0] * K[0] + rho[1] * K[1]) + rho[2] * K[2]) + HPSDF_SURFACE_ETA * K[3];
+        const double d = eval(t.coeffs + rec.a, (int)rec.b, uc[0], uc[1], uc[2], ld) - iso;
+        int sg;
+        if (d > bound)
+            sg = 1;
+        else if (-d > bound)
+            sg = -1;
+        else
+            return 0;  // (a NaN lands here too)
+        if (sign != 0 && sg != sign) return 0;
+        sign = sg;
+    }
+    return sign == 0 ? 0 : (sign > 0 ? 1 : 2);
+}
+
+struct DevEval {
+    const double* sNl;
+    const double* sRec;
+    __device__ double operator()(const double* c, int degree, double ux, double uy, double uz, int depth) const {
+        return evalLeaf<12>(c, degree, ux, uy, uz, depth, sNl, sRec);
+    }
+};
+
+// hostQueryPoint's statements (host_query.cpp): FApprox, Octree.cpp:859-901
+struct HostEval {
+    const Tables* T;
+    double operator()(const double* c, int degree, double ux, double uy, double uz, int depth) const {
+        const double u[3] = {ux, uy, uz};
+        double tab[3][13];
+        for (int a = 0; a < 3; ++a) {
+            tab[a][0] = T->normalisedLengths[0][depth];
+            double m2 = 0.0, m1 = 1.0;
+            for (int j = 1; j <= degree; ++j) {
+                const double l = T->recurrence[j][0] * u[a] * m1 - T->recurrence[j][1] * m2;
+                m2 = m1, m1 = l;
+                tab[a][j] = l * T->normalisedLengths[j][depth];
+            }
+        }
+        double f = 0.0;
+        const int n = (int)T->coeffCount[degree];
+        for (int i = 0; i < n; ++i) {
+            double lp = tab[0][T->basisIndex[i][0]];
+            lp = lp * tab[1][T->basisIndex[i][1]];
+            lp = lp * tab[2][T->basisIndex[i][2]];
+            f = f + c[i] * lp;
+        }
+        return f;
+    }
+};
+
+// ---- constants and classes -----------------------------------------------------------------------------------------------------
+
+// depth[i] of every node, handed down from the root level by level by ONE workgroup (a node's record does not hold it)
+__global__ __launch_bounds__(1024) void sparse_depth_kernel(const NodeRec* __restrict__ nodes, uint32_t nNodes, int maxDepth, uint8_t* depth) {
+    for (uint32_t i = threadIdx.x; i < nNodes; i += 1024u) depth[i] = i == 0 ? 0 : 0xFF;
+    __syncthreads();
+    for (int level = 0; level < maxDepth; ++level) {
+        for (uint32_t i = threadIdx.x; i < nNodes; i += 1024u) {
+            const NodeRec rec = nodes[i];
+            if (depth[i] == level && rec.b == kInteriorTag && rec.a < nNodes && nNodes - rec.a >= 8u)
+                for (uint32_t c = 0; c < 8u; ++c) depth[rec.a + c] = (uint8_t)(level + 1);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void sparse_consts_kernel(const NodeRec* __restrict__ nodes, const double* __restrict__ coeffs,
+                                                                 const uint8_t* __restrict__ depth, uint32_t nNodes,
+                                                                 const DeviceTables* __restrict__ T, double* __restrict__ consts) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= nNodes) return;
+    double out[4] = {0.0, 0.0, 0.0, 0.0};
+    const NodeRec rec = nodes[i];
+    const int d = depth[i];
+    if (rec.b <= 12u && d <= HPSDF_TREE_MAX_DEPTH) leafBound(coeffs + rec.a, T->count[rec.b], d, &T->nl[0][0], T->bidx, out);
+    for (int k = 0; k < 4; ++k) consts[4 * (size_t)i + k] = out[k];
+}
+
+__global__ __launch_bounds__(kThreads) void sparse_classify_kernel(ClsTree t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
+                                                                   uint64_t firstBlock, uint64_t count, uint8_t* __restrict__ out,
+                                                                   unsigned long long* __restrict__ visitedTotal) {
+    __shared__ double sNl[13 * 11];
+    __shared__ double sRec[26];
+    stageQueryTables(T, sNl, sRec);
+    __syncthreads();
+    const DevEval eval{sNl, sRec};
+    unsigned long long mine = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < count; i += stride) {
+        uint32_t visited;
+        out[i] = classifyBlock(t, g, iso, firstBlock + i, eval, visited);
+        mine += visited;
+    }
+    if (visitedTotal != nullptr) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+        if ((threadIdx.x & 63u) == 0 && mine != 0) atomicAdd(visitedTotal, mine);
+    }
+}
+
+// ---- the active blocks ---------------------------------------------------------------------------------------------------------
+
+struct PackedCases {
+    uint64_t v[256];
+};
+constexpr PackedCases packCases() {
+    const SurfaceTable T = makeSurfaceTable();
+    PackedCases p{};
+    for (int i = 0; i < 256; ++i) p.v[i] = T.packed[i];
+    return p;
+}
+__constant__ PackedCases kSparseCases = packCases();
+// cube-local edge -> its lower corner and axis (surface_table.hpp's numbering)
+__constant__ uint8_t kSparseEdgeCorner[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
+__constant__ uint8_t kSparseEdgeAxis[12] = {0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2};
+
+struct BlockOut {
+    uint32_t* vcount;  // COUNT: per active block
+    uint32_t* tcount;
+    const uint64_t* vprefix;  // EMIT: exclusive prefixes of the two
+    const uint64_t* tprefix;
+    uint64_t* vkey;  // vertex records: edge id, own position, xyz
+    uint64_t* vidx;
+    double* vxyz;
+    uint64_t* tkey;  // triangle records: 8 Q + index in the cube, own position, three edge ids
+    uint64_t* tidx;
+    uint64_t* tedge;
+};
+
+__device__ __forceinline__ uint32_t rankBelow(uint64_t mask) {  // set bits of the ballot in the lanes below this one
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+template <int MAXP, bool EMIT>
+__global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
+                                                                const uint64_t* __restrict__ active, uint64_t nActive, BlockOut o) {
+    __shared__ double sNl[13 * 11];
+    __shared__ double sRec[26];
+    __shared__ uint64_t sCase[256];
+    __shared__ double sV[kBlockPts];
+    __shared__ uint8_t sIn[kBlockPts + 7];
+    __shared__ uint32_t sVW[4], sTW[kCubeRounds][4];
+    stageQueryTables(T, sNl, sRec);
+    for (uint32_t c = threadIdx.x; c < 256u; c += kThreads) sCase[c] = kSparseCases.v[c];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    for (uint64_t ab = blockIdx.x; ab < nActive; ab += gridDim.x) {
+        __syncthreads();  // the tables are staged; the previous block's LDS is no longer read
+        const uint64_t b = active[ab];
+        const uint64_t br = b / g.nb[0];
+        const uint32_t bi[3] = {(uint32_t)(b - br * g.nb[0]), (uint32_t)(br % g.nb[1]), (uint32_t)(br / g.nb[1])};
+        uint32_t base[3], cnt[3], own[3];
+        for (int a = 0; a < 3; ++a) {
+            base[a] = kB * bi[a];
+            cnt[a] = g.n[a] - base[a] < kB ? g.n[a] - base[a] : kB;  // cubes of the block on this axis
+            own[a] = cnt[a] + (bi[a] + 1u == g.nb[a] ? 1u : 0u);     // points whose edges it owns: the last block also owns the boundary layer
+        }
+        for (uint32_t p = tid; p < kBlockPts; p += kThreads) {
+            const uint32_t lx = p % kP, ly = (p / kP) % kP, lz = p / (kP * kP);
+            double v = 0.0;
+            if (lx <= cnt[0] && ly <= cnt[1] && lz <= cnt[2]) {
+                const double x = g.lo[0] + (double)(base[0] + lx) * g.h[0], y = g.lo[1] + (double)(base[1] + ly) * g.h[1],
+                             z = g.lo[2] + (double)(base[2] + lz) * g.h[2];
+                v = queryPoint<MAXP>(t, x, y, z, sNl, sRec);
+            }
+            sV[p] = v;
+            sIn[p] = v < iso ? 1 : 0;
+        }
+        __syncthreads();
+        // slot e < 3 * 729: point e / 3, axis e % 3.  The block owns the edge if it owns its lower point; the edge exists if it stays in the lattice.
+        auto crosses = [&](uint32_t e, uint32_t& p, uint32_t& ax) -> bool {
+            p = e / 3u, ax = e - 3u * p;
+            if (p >= kBlockPts) return false;
+            const uint32_t l[3] = {p % kP, (p / kP) % kP, p / (kP * kP)};
+            if (!(l[0] < own[0] && l[1] < own[1] && l[2] < own[2] && l[ax] < cnt[ax])) return false;
+            const uint32_t s = ax == 0 ? 1u : (ax == 1 ? kP : kP * kP);
+            return sIn[p] != sIn[p + s];
+        };
+        auto cubeCase = [&](uint32_t c, uint32_t (&l)[3]) -> uint64_t {  // packed case of cube slot c, 0 outside the block
+            l[0] = c % kB, l[1] = (c / kB) % kB, l[2] = c / (kB * kB);
+            if (!(l[0] < cnt[0] && l[1] < cnt[1] && l[2] < cnt[2])) return 0;
+            const uint32_t p = l[0] + kP * (l[1] + kP * l[2]);
+            uint32_t cs = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; ++k) cs |= (uint32_t)sIn[p + (k & 1u) + kP * ((k >> 1) & 1u) + kP * kP * (k >> 2)] << k;
+            return sCase[cs];
+        };
+        uint32_t vw = 0;
+        for (uint32_t r = 0; r < kEdgeRounds; ++r) {
+            uint32_t p, ax;
+            vw += (uint32_t)__popcll(__ballot(crosses(r * kThreads + tid, p, ax)));
+        }
+        uint32_t tn[kCubeRounds];
+        uint64_t pk[kCubeRounds];
+        uint32_t cl[kCubeRounds][3];
+        for (uint32_t r = 0; r < kCubeRounds; ++r) {
+            pk[r] = cubeCase(r * kThreads + tid, cl[r]);
+            tn[r] = (uint32_t)(pk[r] & 7u);
+            uint32_t sum = tn[r];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+            if (lane == 0) sTW[r][wave] = sum;
+        }
+        if (lane == 0) sVW[wave] = vw;
+        __syncthreads();
+        if constexpr (!EMIT) {
+            if (tid == 0) {
+                o.vcount[ab] = sVW[0] + sVW[1] + sVW[2] + sVW[3];
+                uint32_t ts = 0;
+                for (uint32_t r = 0; r < kCubeRounds; ++r) ts += sTW[r][0] + sTW[r][1] + sTW[r][2] + sTW[r][3];
+                o.tcount[ab] = ts;
+            }
+        } else {
+            uint64_t vpos = o.vprefix[ab];
+            for (uint32_t w = 0; w < wave; ++w) vpos += sVW[w];
+            for (uint32_t r = 0; r < kEdgeRounds; ++r) {
+                uint32_t p, ax;
+                const bool c = crosses(r * kThreads + tid, p, ax);
+                const uint64_t m = __ballot(c);
+                if (c) {
+                    const uint64_t at = vpos + rankBelow(m);
+                    const uint32_t l[3] = {p % kP, (p / kP) % kP, p / (kP * kP)};
+                    const uint32_t idx[3] = {base[0] + l[0], base[1] + l[1], base[2] + l[2]};
+                    const uint32_t s = ax == 0 ? 1u : (ax == 1 ? kP : kP * kP);
+                    // hpsdf_extract_surface's vertex (surface.hip, surf_vertex_kernel): the same statements
+                    const double va = sV[p], vb = sV[p + s];
+                    const double tt = (iso - va) / (vb - va);
+                    double q[3];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) q[d] = g.lo[d] + (double)idx[d] * g.h[d];
+                    const double xb = g.lo[ax] + (double)(idx[ax] + 1u) * g.h[ax];
+                    q[ax] = q[ax] + tt * (xb - q[ax]);
+                    o.vkey[at] = 3u * (idx[0] + g.np[0] * (idx[1] + g.np[1] * (uint64_t)idx[2])) + ax;
+                    o.vidx[at] = at;
+                    o.vxyz[3 * at] = q[0], o.vxyz[3 * at + 1] = q[1], o.vxyz[3 * at + 2] = q[2];
+                }
+                vpos += (uint64_t)__popcll(m);
+            }
+            uint64_t tpos = o.tprefix[ab];
+            for (uint32_t r = 0; r < kCubeRounds; ++r) {
+                uint32_t incl = tn[r];  // inclusive sum over the wave's lanes
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t y = __shfl_up(incl, off, 64);
+                    if (lane >= (uint32_t)off) incl += y;
+                }
+                uint64_t at = tpos + (incl - tn[r]);
+                for (uint32_t w = 0; w < wave; ++w) at += sTW[r][w];
+                if (tn[r] != 0) {
+                    const uint32_t i = base[0] + cl[r][0], j = base[1] + cl[r][1], k = base[2] + cl[r][2];
+                    const uint64_t Q = i + g.n[0] * (j + g.n[1] * (uint64_t)k);
+                    for (uint32_t tr = 0; tr < tn[r]; ++tr) {
+                        o.tkey[at + tr] = 8u * Q + tr;
+                        o.tidx[at + tr] = at + tr;
+#pragma unroll
+                        for (int m = 0; m < 3; ++m) {
+                            const uint32_t le = (uint32_t)(pk[r] >> (3 + 12 * tr + 4 * m)) & 15u;
+                            const uint32_t cr = kSparseEdgeCorner[le];
+                            const uint64_t L = (i + (cr & 1u)) + g.np[0] * ((j + ((cr >> 1) & 1u)) + g.np[1] * (uint64_t)(k + (cr >> 2)));
+                            o.tedge[3 * (at + tr) + m] = 3u * L + kSparseEdgeAxis[le];
+                        }
+                    }
+                }
+                tpos += sTW[r][0] + sTW[r][1] + sTW[r][2] + sTW[r][3];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void sparse_gather_kernel(const uint64_t* __restrict__ order, const double* __restrict__ xyz, uint64_t n,
+                                                                 double* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+        const uint64_t s = order[i];
+        out[3 * i] = xyz[3 * s], out[3 * i + 1] = xyz[3 * s + 1], out[3 * i + 2] = xyz[3 * s + 2];
+    }
+}
+
+// triangle i of the sorted order: its three edge ids -> their ranks among the sorted vertex keys (every one of them is there)
+__global__ __launch_bounds__(kThreads) void sparse_renumber_kernel(const uint64_t* __restrict__ order, const uint64_t* __restrict__ tedge, uint64_t nTris,
+                                                                   const uint64_t* __restrict__ vkeys, uint64_t nVerts, uint64_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < nTris; i += stride) {
+        const uint64_t s = order[i];
+        for (int m = 0; m < 3; ++m) {
+            const uint64_t e = tedge[3 * s + m];
+            uint64_t lo = 0, hi = nVerts;  // first position whose key is >= e
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (vkeys[mid] < e)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            out[3 * i + m] = lo;
+        }
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+
+struct IsActive {
+    __host__ __device__ uint64_t operator()(uint8_t c) const { return c == 0 ? 1u : 0u; }
+};
+struct IsActiveFlag {
+    __host__ __device__ bool operator()(uint8_t c) const { return c == 0; }
+};
+
+unsigned gridOf(uint64_t threads, unsigned cap = 65536) {
+    const uint64_t b = (threads + kThreads - 1) / kThreads;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+bool inRoot(const double* rc, const double* ris, int a, double x) {  // Query's f32 containment test on one coordinate
+    const float f = (float)((x - rc[a]) * ris[a]);
+    return f >= -0.5f && f <= 0.5f;
+}
+
+// the arguments of the three entry points -> the lattice; what: the entry point's name for the messages
+int makeLattice(const char* what, const double* rc, const double* ris, const double* lo, const double* hi, const uint32_t* n, double iso,
+                SparseLattice* out, uint64_t* nPtsOut, uint64_t* nCubesOut) {
+    const std::string w = std::string(what) + ": ";
+    if (!std::isfinite(iso)) return fail(HPSDF_ERR_INVALID_ARGUMENT, w + "iso must be finite");
+    static const char* kAxis[3] = {"x", "y", "z"};
+    SparseLattice g{};
+    uint64_t nPts = 1, nCubes = 1;
+    g.nBlocks = 1;
+    for (int a = 0; a < 3; ++a) {
+        const std::string ax = w + "axis " + kAxis[a] + ": ";
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo and hi must be finite");
+        if (!(lo[a] < hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo must be below hi");
+        if (n[a] < 1) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "n must be at least 1");
+        if (n[a] > (1u << 20)) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "n must be at most 2^20");
+        nPts *= (uint64_t)n[a] + 1u;  // (< 2^63: three factors below 2^21)
+        nCubes *= n[a];
+        g.lo[a] = lo[a];
+        g.h[a] = (hi[a] - lo[a]) / (double)n[a];
+        g.n[a] = n[a];
+        g.np[a] = (uint64_t)n[a] + 1u;
+        g.nb[a] = (n[a] + kB - 1) / kB;
+        g.nBlocks *= g.nb[a];
+    }
+    if (nPts > (1ull << 40)) return fail(HPSDF_ERR_INVALID_ARGUMENT, w + "more than 2^40 lattice points");
+    for (int a = 0; a < 3; ++a) {
+        // the containment test is monotone along an axis: the two extreme lattice points decide for all of them
+        const double last = g.lo[a] + (double)n[a] * g.h[a];
+        if (!inRoot(rc, ris, a, g.lo[a]) || !inRoot(rc, ris, a, last))
+            return fail(HPSDF_ERR_INVALID_ARGUMENT, w + "axis " + kAxis[a] + ": the box leaves the tree's root (Query would return DBL_MAX there)");
+    }
+    *out = g;
+    if (nPtsOut) *nPtsOut = nPts;
+    if (nCubesOut) *nCubesOut = nCubes;
+    return HPSDF_OK;
+}
+
+// The call's device memory: what is live, the most that was, and everything freed when the call ends.
+struct DevPool {
+    std::vector<std::pair<void*, size_t>> live;
+    size_t cur = 0, peak = 0;
+    bool oom = false;
+    hipError_t alloc(void** p, size_t bytes) {
+        *p = nullptr;
+        const hipError_t e = hipMalloc(p, bytes < 256 ? 256 : bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            oom = e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
+            return e;
+        }
+        live.emplace_back(*p, bytes);
+        cur += bytes;
+        peak = cur > peak ? cur : peak;
+        return hipSuccess;
+    }
+    void release(void* p) {
+        for (auto& x : live)
+            if (x.first == p && p != nullptr) {
+                (void)hipFree(p);
+                cur -= x.second;
+                x = live.back();
+                live.pop_back();
+                return;
+            }
+    }
+    ~DevPool() {
+        for (auto& x : live) (void)hipFree(x.first);
+    }
+};
+
+#define SPARSE_ALLOC(pool, ptr, bytes, name)                                                                        \
+    do {                                                                                                            \
+        const hipError_t ea_ = (pool).alloc((void**)&(ptr), (bytes));                                                \
+        if (ea_ != hipSuccess && (pool).oom)                                                                         \
+            return fail(HPSDF_ERR_OUT_OF_MEMORY, std::string(kWhat) + ": out of device memory (" + (name) + ")"); \
+        HPSDF_HIP(ea_);                                                                                             \
+    } while (0)
+
+struct Events {
+    static constexpr int kN = 10;
+    hipEvent_t e[kN] = {};
+    bool ok = true;
+    Events() {
+        for (auto& x : e)
+            if (hipEventCreate(&x) != hipSuccess) x = nullptr, ok = false;
+        if (!ok) (void)hipGetLastError();
+    }
+    ~Events() {
+        for (auto& x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    void mark(int i, hipStream_t s) {
+        if (ok && hipEventRecord(e[i], s) != hipSuccess) ok = false;
+    }
+    double ms(int a, int b) const {
+        float r = 0.0f;
+        return ok && hipEventElapsedTime(&r, e[a], e[b]) == hipSuccess ? (double)r : 0.0;
+    }
+};
+
+struct HostOut {  // malloc'd outputs, released unless handed to the caller
+    void* p = nullptr;
+    ~HostOut() { std::free(p); }
+};
+
+unsigned bitsFor(uint64_t maxKey) {  // radix passes stop at the highest bit a key can have
+    unsigned b = 1;
+    while (b < 64 && (maxKey >> b) != 0) ++b;
+    return b;
+}
+
+// constants of the tree's leaves and the classes of blocks [first, first + count) into dClass; the stream is not synchronised
+int classifyOnDevice(const char* kWhat, hpsdf_ctx* ctx, const hpsdf_tree* t, DevPool& pool, const SparseLattice& g, double iso, uint64_t first,
+                     uint64_t count, uint8_t* dClass, unsigned long long* dVisited) {
+    hipStream_t s = ctx->stream;
+    const uint32_t nNodes = (uint32_t)t->nNodes;
+    uint8_t* dDepth = nullptr;
+    double* dConsts = nullptr;
+    SPARSE_ALLOC(pool, dDepth, (size_t)nNodes, "node depths");
+    SPARSE_ALLOC(pool, dConsts, (size_t)nNodes * 4 * sizeof(double), "leaf constants");
+    hipLaunchKernelGGL(sparse_depth_kernel, dim3(1), dim3(1024), 0, s, t->dev.nodes, nNodes, t->maxDepth, dDepth);
+    HPSDF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sparse_consts_kernel, dim3(gridOf(nNodes, 1u << 24)), dim3(kThreads), 0, s, t->dev.nodes, t->dev.coeffs, dDepth, nNodes,
+                       ctx->dTables, dConsts);
+    HPSDF_HIP(hipGetLastError());
+    ClsTree ct{};
+    ct.nodes = t->dev.nodes, ct.coeffs = t->dev.coeffs, ct.consts = dConsts;
+    for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
+    hipLaunchKernelGGL(sparse_classify_kernel, dim3(gridOf(count)), dim3(kThreads), 0, s, ct, ctx->dTables, g, iso, first, count, dClass, dVisited);
+    HPSDF_HIP(hipGetLastError());
+    return HPSDF_OK;
+}
+
+template <bool EMIT>
+hipError_t launchBlocks(hipStream_t s, const TreeDev& td, const DeviceTables* T, const SparseLattice& g, double iso, const uint64_t* dActive,
+                        uint64_t nActive, const BlockOut& o) {
+    const dim3 grid((unsigned)(nActive < (1u << 20) ? nActive : (1u << 20))), block(kThreads);
+    if (td.maxDegree <= 3)
+        hipLaunchKernelGGL((sparse_block_kernel<3, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
+    else if (td.maxDegree <= 5)
+        hipLaunchKernelGGL((sparse_block_kernel<5, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
+    else
+        hipLaunchKernelGGL((sparse_block_kernel<12, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
+    return hipGetLastError();
+}
+
+int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const double* hi, const uint32_t* n, double iso, double** verts,
+                  uint64_t* nVerts, uint64_t** tris, uint64_t* nTris, hpsdf_surface_sparse_stats* stats) {
+    static const char* kWhat = "hpsdf_extract_surface_sparse";
+    SparseLattice g{};
+    uint64_t nPts = 0, nCubes = 0;
+    if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, &nPts, &nCubes)) return rc;
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevPool pool;
+    Events ev;
+    TreeDev td = t->dev;
+    td.leftAssoc = reductionLeftAssoc(ctx);
+    hpsdf_surface_sparse_stats st{};
+    st.blocks = g.nBlocks;
+
+    // classes
+    uint8_t* dClass = nullptr;
+    unsigned long long* dScalars = nullptr;  // [0] visited leaves, [1] active blocks, [2] selected count
+    SPARSE_ALLOC(pool, dClass, (size_t)g.nBlocks, "block classes");
+    SPARSE_ALLOC(pool, dScalars, 3 * sizeof(unsigned long long), "counters");
+    ev.mark(0, s);
+    HPSDF_HIP(hipMemsetAsync(dScalars, 0, 3 * sizeof(unsigned long long), s));
+    if (const int rc = classifyOnDevice(kWhat, ctx, t, pool, g, iso, 0, g.nBlocks, dClass, dScalars)) return rc;
+    ev.mark(1, s);
+
+    // the active blocks, in block order
+    using ActiveCount = rocprim::transform_iterator<const uint8_t*, IsActive, uint64_t>;
+    using ActiveFlag = rocprim::transform_iterator<const uint8_t*, IsActiveFlag, bool>;
+    size_t tmpBytes = 0;
+    HPSDF_HIP(rocprim::reduce(nullptr, tmpBytes, ActiveCount(dClass, IsActive()), (uint64_t*)(dScalars + 1), (uint64_t)0, (size_t)g.nBlocks,
+                              rocprim::plus<uint64_t>(), s));
+    void* dTmp = nullptr;
+    SPARSE_ALLOC(pool, dTmp, tmpBytes, "reduce storage");
+    HPSDF_HIP(rocprim::reduce(dTmp, tmpBytes, ActiveCount(dClass, IsActive()), (uint64_t*)(dScalars + 1), (uint64_t)0, (size_t)g.nBlocks,
+                              rocprim::plus<uint64_t>(), s));
+    unsigned long long scal[2] = {0, 0};
+    HPSDF_HIP(hipMemcpyAsync(scal, dScalars, sizeof scal, hipMemcpyDeviceToHost, s));
+    HPSDF_HIP(hipStreamSynchronize(s));
+    pool.release(dTmp);
+    st.leaves_visited = scal[0];
+    st.active_blocks = scal[1];
+    const uint64_t nActive = scal[1];
+
+    uint64_t V = 0, T = 0;
+    uint64_t *dActive = nullptr, *dVp = nullptr, *dTp = nullptr;
+    if (nActive > 0) {
+        SPARSE_ALLOC(pool, dActive, nActive * 8, "active blocks");
+        tmpBytes = 0;
+        HPSDF_HIP(rocprim::select(nullptr, tmpBytes, rocprim::counting_iterator<uint64_t>(0), ActiveFlag(dClass, IsActiveFlag()), dActive,
+                                  (uint64_t*)(dScalars + 2), (size_t)g.nBlocks, s));
+        SPARSE_ALLOC(pool, dTmp, tmpBytes, "select storage");
+        HPSDF_HIP(rocprim::select(dTmp, tmpBytes, rocprim::counting_iterator<uint64_t>(0), ActiveFlag(dClass, IsActiveFlag()), dActive,
+                                  (uint64_t*)(dScalars + 2), (size_t)g.nBlocks, s));
+        ev.mark(2, s);
+        // per-block counts and their prefixes
+        uint32_t *dVc = nullptr, *dTc = nullptr;
+        SPARSE_ALLOC(pool, dVc, (nActive + 1) * 4, "vertex counts");
+        SPARSE_ALLOC(pool, dTc, (nActive + 1) * 4, "triangle counts");
+        SPARSE_ALLOC(pool, dVp, (nActive + 1) * 8, "vertex prefixes");
+        SPARSE_ALLOC(pool, dTp, (nActive + 1) * 8, "triangle prefixes");
+        HPSDF_HIP(hipMemsetAsync(dVc + nActive, 0, 4, s));
+        HPSDF_HIP(hipMemsetAsync(dTc + nActive, 0, 4, s));
+        BlockOut o{};
+        o.vcount = dVc, o.tcount = dTc;
+        HPSDF_HIP(launchBlocks<false>(s, td, ctx->dTables, g, iso, dActive, nActive, o));
+        ev.mark(3, s);
+        HPSDF_HIP(hipStreamSynchronize(s));  // (select's storage is free again)
+        pool.release(dTmp);
+        pool.release(dClass);
+        dClass = nullptr;
+        tmpBytes = 0;
+        HPSDF_HIP(rocprim::exclusive_scan(nullptr, tmpBytes, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(nActive + 1),
+                                          rocprim::plus<uint64_t>(), s));
+        SPARSE_ALLOC(pool, dTmp, tmpBytes, "scan storage");
+        HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpBytes, dVc, dVp, (uint64_t)0, (size_t)(nActive + 1), rocprim::plus<uint64_t>(), s));
+        HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpBytes, dTc, dTp, (uint64_t)0, (size_t)(nActive + 1), rocprim::plus<uint64_t>(), s));
+        ev.mark(4, s);
+        HPSDF_HIP(hipMemcpyAsync(&V, dVp + nActive, 8, hipMemcpyDeviceToHost, s));
+        HPSDF_HIP(hipMemcpyAsync(&T, dTp + nActive, 8, hipMemcpyDeviceToHost, s));
+        HPSDF_HIP(hipStreamSynchronize(s));
+        pool.release(dTmp);
+        pool.release(dVc);
+        pool.release(dTc);
+        st.classify_ms = ev.ms(0, 1), st.scan_ms = ev.ms(1, 2) + ev.ms(3, 4), st.count_ms = ev.ms(2, 3);
+    } else {
+        st.classify_ms = ev.ms(0, 1);
+    }
+
+    HostOut hv, ht;
+    if (T > 0) {
+        hv.p = std::malloc(V * 3 * sizeof(double));
+        ht.p = std::malloc(T * 3 * sizeof(uint64_t));
+        if (!hv.p || !ht.p) return fail(HPSDF_ERR_OUT_OF_MEMORY, std::string(kWhat) + ": host allocation failed");
+        // records
+        BlockOut o{};
+        o.vprefix = dVp, o.tprefix = dTp;
+        SPARSE_ALLOC(pool, o.vkey, V * 8, "vertex keys");
+        SPARSE_ALLOC(pool, o.vidx, V * 8, "vertex indices");
+        SPARSE_ALLOC(pool, o.vxyz, V * 24, "vertex records");
+        SPARSE_ALLOC(pool, o.tkey, T * 8, "triangle keys");
+        SPARSE_ALLOC(pool, o.tidx, T * 8, "triangle indices");
+        SPARSE_ALLOC(pool, o.tedge, T * 24, "triangle records");
+        ev.mark(5, s);
+        HPSDF_HIP(launchBlocks<true>(s, td, ctx->dTables, g, iso, dActive, nActive, o));
+        ev.mark(6, s);
+        // vertices in edge-id order
+        uint64_t *dVkS = nullptr, *dViS = nullptr, *dTkS = nullptr, *dTiS = nullptr;
+        double* dVerts = nullptr;
+        uint64_t* dTris = nullptr;
+        const unsigned vBits = bitsFor(3 * nPts), tBits = bitsFor(8 * nCubes);
+        SPARSE_ALLOC(pool, dVkS, V * 8, "sorted vertex keys");
+        SPARSE_ALLOC(pool, dViS, V * 8, "sorted vertex indices");
+        tmpBytes = 0;
+        HPSDF_HIP(rocprim::radix_sort_pairs(nullptr, tmpBytes, o.vkey, dVkS, o.vidx, dViS, (size_t)V, 0u, vBits, s));
+        SPARSE_ALLOC(pool, dTmp, tmpBytes, "sort storage");
+        HPSDF_HIP(rocprim::radix_sort_pairs(dTmp, tmpBytes, o.vkey, dVkS, o.vidx, dViS, (size_t)V, 0u, vBits, s));
+        HPSDF_HIP(hipStreamSynchronize(s));
+        pool.release(dTmp);
+        pool.release(o.vkey);
+        pool.release(o.vidx);
+        pool.release(dActive);
+        pool.release(dVp);
+        pool.release(dTp);
+        SPARSE_ALLOC(pool, dVerts, V * 24, "vertices");
+        hipLaunchKernelGGL(sparse_gather_kernel, dim3(gridOf(V)), dim3(kThreads), 0, s, dViS, o.vxyz, V, dVerts);
+        HPSDF_HIP(hipGetLastError());
+        // triangles in key order, renumbered
+        SPARSE_ALLOC(pool, dTkS, T * 8, "sorted triangle keys");
+        SPARSE_ALLOC(pool, dTiS, T * 8, "sorted triangle indices");
+        tmpBytes = 0;
+        HPSDF_HIP(rocprim::radix_sort_pairs(nullptr, tmpBytes, o.tkey, dTkS, o.tidx, dTiS, (size_t)T, 0u, tBits, s));
+        SPARSE_ALLOC(pool, dTmp, tmpBytes, "sort storage");
+        HPSDF_HIP(rocprim::radix_sort_pairs(dTmp, tmpBytes, o.tkey, dTkS, o.tidx, dTiS, (size_t)T, 0u, tBits, s));
+        HPSDF_HIP(hipStreamSynchronize(s));
+        pool.release(dTmp);
+        pool.release(o.tkey);
+        pool.release(o.tidx);
+        pool.release(dTkS);
+        pool.release(o.vxyz);
+        pool.release(dViS);
+        SPARSE_ALLOC(pool, dTris, T * 24, "triangles");
+        hipLaunchKernelGGL(sparse_renumber_kernel, dim3(gridOf(T)), dim3(kThreads), 0, s, dTiS, o.tedge, T, dVkS, V, dTris);
+        HPSDF_HIP(hipGetLastError());
+        ev.mark(7, s);
+        HPSDF_HIP(hipMemcpyAsync(hv.p, dVerts, V * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HPSDF_HIP(hipMemcpyAsync(ht.p, dTris, T * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        ev.mark(8, s);
+        HPSDF_HIP(hipStreamSynchronize(s));
+        st.emit_ms = ev.ms(5, 6), st.sort_ms = ev.ms(6, 7), st.download_ms = ev.ms(7, 8), st.total_ms = ev.ms(0, 8);
+        *verts = (double*)hv.p, *tris = (uint64_t*)ht.p;
+        hv.p = nullptr, ht.p = nullptr;
+        *nVerts = V, *nTris = T;
+    } else {
+        ev.mark(8, s);
+        HPSDF_HIP(hipStreamSynchronize(s));
+        st.total_ms = ev.ms(0, 8);
+    }
+    st.peak_scratch_bytes = pool.peak;
+    if (stats) *stats = st;
+    return HPSDF_OK;
+}
+
+// a serialised block -> the arrays the walk reads, as hpsdf_tree_upload lays them out (capi.cpp) -- with the constants
+struct HostTree {
+    std::vector<NodeRec> recs;
+    std::vector<double> padded, consts;
+    ClsTree view{};
+};
+
+int parseBlock(const void* block, size_t size, HostTree* out) {
+    if (!block || size < 16 + sizeof(hpsdf_config)) return fail(HPSDF_ERR_BAD_BLOCK, "block too small");
+    const uint8_t* p = (const uint8_t*)block;
+    uint64_t nCoeffs, nNodes;
+    std::memcpy(&nCoeffs, p, 8);
+    if (nCoeffs > (size - 16 - sizeof(hpsdf_config)) / 8) return fail(HPSDF_ERR_BAD_BLOCK, "coefficient count exceeds block");
+    std::memcpy(&nNodes, p + 8 + 8 * nCoeffs, 8);
+    if (nNodes == 0 || nNodes > (size_t)0xFFFFFFF0u || (size - 16 - sizeof(hpsdf_config) - 8 * (size_t)nCoeffs) / sizeof(hpsdf_node) < nNodes ||
+        8 + 8 * (size_t)nCoeffs + 8 + sizeof(hpsdf_node) * (size_t)nNodes + sizeof(hpsdf_config) != size)
+        return fail(HPSDF_ERR_BAD_BLOCK, "node count does not match block size");
+    if (nCoeffs > 0xFFFFFFFFull) return fail(HPSDF_ERR_UNSUPPORTED, "more than 2^32 coefficients");
+    std::vector<double> coeffs(nCoeffs);
+    if (nCoeffs) std::memcpy(coeffs.data(), p + 8, 8 * nCoeffs);
+    std::vector<hpsdf_node> nodes(nNodes);
+    std::memcpy(nodes.data(), p + 16 + 8 * nCoeffs, sizeof(hpsdf_node) * nNodes);
+    hpsdf_config cfg;
+    std::memcpy(&cfg, p + 16 + 8 * nCoeffs + sizeof(hpsdf_node) * nNodes, sizeof cfg);
+    const Tables& T = tables();
+    if (nodes[0].degree != kInteriorDegree || nNodes < 9) return fail(HPSDF_ERR_UNSUPPORTED, "root must be an interior node (Octree::CreateRoot always splits it)");
+    BlockTreeInfo walk;
+    {
+        std::string why;
+        const int vrc = checkBlockTree(nodes.data(), nNodes, nCoeffs, T.coeffCount, false, false, &walk, why);
+        if (vrc) return fail(vrc, why);
+    }
+    uint8_t bidx[kMaxCoeffs][4];
+    for (int i = 0; i < kMaxCoeffs; ++i)
+        for (int k = 0; k < 3; ++k) bidx[i][k] = (uint8_t)T.basisIndex[i][k];
+    out->recs.assign(nNodes, NodeRec{0, 0});
+    out->consts.assign(4 * (size_t)nNodes, 0.0);
+    out->padded.clear();
+    out->padded.reserve(nCoeffs + 16 * nNodes);
+    for (const uint64_t i : walk.order) {
+        const hpsdf_node& nd = nodes[i];
+        if (nd.degree == kInteriorDegree) {
+            out->recs[i] = NodeRec{(uint32_t)nd.child_idx, kInteriorTag};
+        } else {
+            out->recs[i] = NodeRec{(uint32_t)out->padded.size(), (uint32_t)nd.degree};
+            out->padded.insert(out->padded.end(), coeffs.begin() + nd.coeffs_start, coeffs.begin() + nd.coeffs_start + T.coeffCount[nd.degree]);
+            out->padded.resize((out->padded.size() + 15) & ~(size_t)15, 0.0);
+        }
+    }
+    for (const uint64_t i : walk.order) {
+        const NodeRec rec = out->recs[i];
+        if (rec.b <= 12u && walk.depthOf[i] <= HPSDF_TREE_MAX_DEPTH)
+            leafBound(out->padded.data() + rec.a, (uint32_t)T.coeffCount[rec.b], walk.depthOf[i], &T.normalisedLengths[0][0], bidx,
+                      out->consts.data() + 4 * i);
+    }
+    out->view.nodes = out->recs.data();
+    out->view.coeffs = out->padded.data();
+    out->view.consts = out->consts.data();
+    for (int a = 0; a < 3; ++a) {
+        out->view.rootCentre[a] = (double)((cfg.root_min[a] + cfg.root_max[a]) / 2.0f);  // Octree.cpp:419
+        out->view.rootInvSizes[a] = (double)(1.0f / (cfg.root_max[a] - cfg.root_min[a]));  // Octree.cpp:420
+    }
+    return HPSDF_OK;
+}
+
+}  // namespace
+
+}  // namespace hpsdf
+
+using namespace hpsdf;
+
+extern "C" {
+
+int hpsdf_extract_surface_sparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
+                                 double** verts, uint64_t* nVerts, uint64_t** tris, uint64_t* nTris, hpsdf_surface_sparse_stats* stats) {
+    try {
+        if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+        if (!t || !lo || !hi || !n || !verts || !nVerts || !tris || !nTris) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+        *verts = nullptr, *tris = nullptr, *nVerts = 0, *nTris = 0;
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+        return extractSparse(ctx, t, lo, hi, n, iso, verts, nVerts, tris, nTris, stats);
+    } catch (const std::bad_alloc&) {
+        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
+    } catch (const std::exception& ex) {
+        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
+    }
+}
+
+int hpsdf_surface_classify_host(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
+                                uint64_t first_block, uint64_t count, uint8_t* out) {
+    try {
+        static const char* kWhat = "hpsdf_surface_classify_host";
+        if (!lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+        HostTree ht;
+        if (const int rc = parseBlock(block, size, &ht)) return rc;
+        SparseLattice g{};
+        if (const int rc = makeLattice(kWhat, ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
+        if (first_block > g.nBlocks || count > g.nBlocks - first_block)
+            return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
+        const HostEval eval{&tables()};
+        for (uint64_t i = 0; i < count; ++i) {
+            uint32_t visited;
+            out[i] = classifyBlock(ht.view, g, iso, first_block + i, eval, visited);
+        }
+        return HPSDF_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
+    } catch (const std::exception& ex) {
+        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
+    }
+}
+
+int hpsdf_surface_classify_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
+                                  uint64_t first_block, uint64_t count, uint8_t* out) {
+    try {
+        static const char* kWhat = "hpsdf_surface_classify_device";
+        if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+        if (!t || !lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+        if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+        SparseLattice g{};
+        if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
+        if (first_block > g.nBlocks || count > g.nBlocks - first_block)
+            return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
+        if (count == 0) return HPSDF_OK;
+        HPSDF_HIP(hipSetDevice(ctx->device));
+        DevPool pool;
+        uint8_t* dClass = nullptr;
+        SPARSE_ALLOC(pool, dClass, (size_t)count, "block classes");
+        if (const int rc = classifyOnDevice(kWhat, ctx, t, pool, g, iso, first_block, count, dClass, nullptr)) return rc;
+        HPSDF_HIP(hipMemcpyAsync(out, dClass, (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+        HPSDF_HIP(hipStreamSynchronize(ctx->stream));
+        return HPSDF_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
+    } catch (const std::exception& ex) {
+        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
+    }
+}
+
+}  // extern "C"

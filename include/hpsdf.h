@@ -358,6 +358,66 @@ HPSDF_API int hpsdf_extract_surface(hpsdf_ctx* ctx, const hpsdf_tree* t, const d
  * [2] scans, [3] vertex and triangle output, [4] download, [5] the whole call from its first launch (events on the context stream) */
 HPSDF_API int hpsdf_surface_last_timings(double ms[6]);
 
+/* ---- sparse ExtractSurface: the same mesh, evaluated only where the tree cannot rule the surface out --------------------------------
+ * Same geometry as hpsdf_extract_surface: the lattice, the point arithmetic lo + (double)i * h, the classification v < iso, the vertex
+ * arithmetic, the case table, the edge ids 3 L + axis, vertices in increasing edge id, triangles by cube Q then in case-table order,
+ * the winding, malloc'd outputs and the empty result (HPSDF_OK, counts 0, NULL pointers).  For any arguments the dense call accepts
+ * the sparse call returns bitwise the same verts and tris.  There is no values output; the limits are (n0+1)(n1+1)(n2+1) <= 2^40 and
+ * n[a] <= 2^20 (edge ids and cube keys then fit 43 bits); the containment requirement on the two extreme lattice points is the dense
+ * call's.  Failures as there: nothing stays allocated, the context stays usable, HPSDF_ERR_INVALID_ARGUMENT or
+ * HPSDF_ERR_OUT_OF_MEMORY.
+ * Blocks: HPSDF_SURFACE_BLOCK cubes per axis; block (bx, by, bz) covers cubes [8 b, min(8 b + 8, n)) per axis, its closed point range
+ * is one point wider on the upper side; block index bx + nb0 (by + nb1 bz), nb[a] = ceil(n[a] / 8).
+ * Block classes: 0 must be evaluated; 1 every lattice point of the closed range has v >= iso; 2 every one has v < iso.  1 and 2 are
+ * given only when proven, by this bound.  A leaf of degree p at depth d is f(u) = sum_r c_r prod_b nl[k_b(r)][d] P_{k_b(r)}(u_b) in
+ * its unit coordinates u (P_k: Legendre).  On [-1, 1], |P_k| <= 1 and |P_k'| <= k (k + 1) / 2, so with
+ *     G_a = sum_r |c_r| prod_b nl[k_b(r)][d] k_a(r) (k_a(r) + 1) / 2        and        S = sum_r |c_r| prod_b nl[k_b(r)][d]
+ * every u of a box of half-extents rho_a around u_c has |f(u) - f(u_c)| <= sum_a rho_a G_a (mean value theorem along the segment).
+ * One lane per block walks the tree from the root with the block's two extreme lattice points pushed through Query's own
+ * expressions p = (x - rootCentre) * rootInvSizes and "p >= centre" -- monotone per axis, so on an axis the lower child is visited if
+ * p_lo < c and the upper one if p_hi >= c: a superset of the leaves any lattice point of the block reaches.  In each visited leaf the
+ * block's range in unit coordinates (again Query's expression (p - centre) * (2 << depth) on the extreme points, monotone too) is
+ * clipped to [-(1 + E), 1 + E], f_c is the leaf's polynomial at the clipped box's centre (the leaf evaluation Query uses) and the
+ * leaf passes if
+ *     |f_c - iso| > HPSDF_SURFACE_SLACK * sum_a rho_a G_a + HPSDF_SURFACE_ETA * S.
+ * The block is class 1 (2) if every visited leaf passes with f_c > iso (< iso); class 0 if a leaf fails, the signs differ, more than
+ * HPSDF_SURFACE_MAX_LEAVES leaves are visited or a corner fails the containment test.
+ * The slack, derived (not tuned).  E = 2^-14: the f32 containment test admits p up to 0.5 + 2^-25 (half an f32 ulp above 0.5), which
+ * the deepest leaf (depth 10, scale 2^11) sees as |u| <= 1 + 2^-14; inside the root Query's comparisons keep |u| <= 1.  A polynomial
+ * of degree k bounded by M on [-1, 1] is bounded by M T_k(x) at |x| > 1 (Chebyshev's extremal property), so on [-(1 + E), 1 + E]
+ * |P_k| <= tau and |P_k'| <= tau k (k + 1) / 2 with tau = T_12(1 + 2^-14) = cosh(12 acosh(1 + 2^-14)) < 1.0089.  Every term of
+ * df/du_a is one derivative times two values: sup |df/du_a| <= tau^3 G_a < 1.0268 G_a.  HPSDF_SURFACE_SLACK = 1 + 2^-5 = 1.03125
+ * covers that and leaves 0.4 % for the roundings of G_a (455 positive terms), of the centre and of the half-extents (a few ulps
+ * each).  HPSDF_SURFACE_ETA = 2^-32 covers the difference between the computed and the exact polynomial at the lattice points and
+ * at the centre: the recurrence to degree 12 and the three-factor products err by less than 2^11 ulps of a term, the sum of up to
+ * 455 terms by 2^9 more, both relative to tau^3 S -- under 2^-41 S an evaluation, 2^-40 S for the two; 2^-32 is 2^8 above that.
+ * Device scratch: one class byte per block, 40 bytes per tree node for the constants, 8 + 8 bytes per active block and its two
+ * prefixes, 80 bytes a vertex and 88 a triangle while they are sorted (keys, indices and their sorted copies, records, outputs) plus
+ * rocPRIM's temporaries -- nothing else grows with the lattice's volume (the dense call: under 10 bytes a lattice point).  All of it
+ * is freed before the call returns; stats->peak_scratch_bytes is the most the call held at once, outputs included. */
+#define HPSDF_SURFACE_BLOCK 8
+#define HPSDF_SURFACE_MAX_LEAVES 64
+#define HPSDF_SURFACE_SLACK 1.03125              /* 1 + 2^-5 */
+#define HPSDF_SURFACE_ETA 2.3283064365386963e-10 /* 2^-32 */
+typedef struct hpsdf_surface_sparse_stats { /* 96 bytes */
+    uint64_t blocks, active_blocks; /* all blocks; blocks of class 0 */
+    uint64_t leaves_visited;        /* by the classification, summed over the blocks */
+    double classify_ms, count_ms, scan_ms, emit_ms, sort_ms, download_ms, total_ms; /* device milliseconds: constants and classes;
+                                       per-block counts; compaction and prefix scans; records; sorts, renumbering and gathers; copies
+                                       to the host; the whole call from its first launch */
+    uint64_t peak_scratch_bytes;
+    uint64_t reserved;
+} hpsdf_surface_sparse_stats;
+HPSDF_API int hpsdf_extract_surface_sparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3],
+                                           const uint32_t n[3], double iso, double** verts, uint64_t* n_verts, uint64_t** tris,
+                                           uint64_t* n_tris, hpsdf_surface_sparse_stats* stats /* may be NULL */);
+/* Diagnostics: the class byte of blocks [first_block, first_block + count) into out (host memory).  _host works from a serialised block
+ * on the calling thread (no device) with the kernel's statements: the same bytes as _device. */
+HPSDF_API int hpsdf_surface_classify_host(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3],
+                                          double iso, uint64_t first_block, uint64_t count, uint8_t* out);
+HPSDF_API int hpsdf_surface_classify_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3],
+                                            const uint32_t n[3], double iso, uint64_t first_block, uint64_t count, uint8_t* out);
+
 /* ---- Create: Octree::Create under the canonical round schedule ---------------
  * (Octree.cpp:312-352, 194-309, 558-659, 804-856, 1007-1093; schedule: DESIGN.md)
  *

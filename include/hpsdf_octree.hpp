@@ -513,8 +513,9 @@ class Octree {
     }
 
     /// Marching cubes over resolution_[a] cubes per axis of area_: the level set {Query = iso_} as a closed, consistently wound
-    /// mesh wherever it stays inside area_ (no reference counterpart; include/hpsdf.h, hpsdf_extract_surface)
-    SurfaceMesh ExtractSurface(const Eigen::AlignedBox3f& area_, const Eigen::Vector3i& resolution_, f64 iso_ = 0.0) const {
+    /// mesh wherever it stays inside area_ (no reference counterpart; include/hpsdf.h, hpsdf_extract_surface).  sparse_: the same
+    /// mesh through hpsdf_extract_surface_sparse -- only the blocks the tree cannot rule out are evaluated, lattices up to 2^40 points
+    SurfaceMesh ExtractSurface(const Eigen::AlignedBox3f& area_, const Eigen::Vector3i& resolution_, f64 iso_ = 0.0, bool sparse_ = false) const {
         hpsdf_tree* t = deviceTree();
         if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
         const double lo[3] = {area_.min()(0), area_.min()(1), area_.min()(2)};
@@ -527,7 +528,8 @@ class Octree {
         double* v = nullptr;
         uint64_t* tr = nullptr;
         uint64_t nv = 0, nt = 0;
-        check(hpsdf_extract_surface(ctx_, t, lo, hi, n, iso_, &v, &nv, &tr, &nt, nullptr));
+        check(sparse_ ? hpsdf_extract_surface_sparse(ctx_, t, lo, hi, n, iso_, &v, &nv, &tr, &nt, nullptr)
+                      : hpsdf_extract_surface(ctx_, t, lo, hi, n, iso_, &v, &nv, &tr, &nt, nullptr));
         SurfaceMesh m;
         if (nt) {
             m.vertices.assign(v, v + 3 * nv);
