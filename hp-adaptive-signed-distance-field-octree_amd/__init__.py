@@ -152,6 +152,9 @@ _SIGNATURES = {
     "hpsdf_query_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hpsdf_query_gradient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "hpsdf_query_gradient_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "hpsdf_query_true_gradient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "hpsdf_query_true_gradient_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "hpsdf_query_true_gradient_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -587,6 +590,20 @@ class DeviceTree:
                                               out.ctypes.data_as(C.c_void_p), grad.ctypes.data_as(C.c_void_p)))
         return out, grad
 
+    def query_gradient(self, pts, unit=False):
+        """QueryGradient (include/hpsdf.h): Query's values and the gradient of the polynomial they come from -- not
+        query_with_gradient's shortcut -> (values f64 [n], grad f64 [n,3]); unit: rows normalised.  Outside the root: DBL_MAX, NaN rows."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        out, grad = np.empty(len(pts)), np.empty((len(pts), 3))
+        check(lib().hpsdf_query_true_gradient_host(self.ctx.handle, self.handle, pts.ctypes.data_as(C.c_void_p), len(pts),
+                                                   GRADIENT_UNIT if unit else 0, out.ctypes.data_as(C.c_void_p), grad.ctypes.data_as(C.c_void_p)))
+        return out, grad
+
+    def query_gradient_device(self, d_xyz_ptr, n, d_out_ptr, d_grad_ptr, unit=False):
+        """Raw device pointers (ints; d_out_ptr may be 0: gradients only); asynchronous on the context stream."""
+        check(lib().hpsdf_query_true_gradient_device(self.ctx.handle, self.handle, C.c_void_p(d_xyz_ptr), n, GRADIENT_UNIT if unit else 0,
+                                                     C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(d_grad_ptr)))
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -996,6 +1013,14 @@ class Octree:
             raise HpsdfError(6, "Query on an empty octree")
         return self._tree.query_with_gradient(pts)
 
+    def QueryGradient(self, pts, unit=False):
+        """The field's true gradient (DeviceTree.query_gradient): one point (3,) -> (float, (3,)), or (n,3) -> (values, grad [n,3])."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        a = np.asarray(pts, np.float64)
+        out, grad = self._tree.query_gradient(a, unit)
+        return (float(out[0]), grad[0]) if a.ndim == 1 else (out, grad)
+
     def QueryRay(self, origins, directions, t_max):
         """Octree::QueryRay (Octree.h:75) for one ray -> (hit, t) or (n,3) arrays -> (hit[n], t[n])."""
         if self._tree is None:
@@ -1013,13 +1038,17 @@ class Octree:
         write_bmp(fname + ".bmp", rgb)
         return rgb
 
-    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False):
+    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False, normals=False):
         """Triangle mesh of the level set {Query = iso} over the box [view_min, view_max] with n cubes per axis (an int or three)
         -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice.  sparse: the same arrays through
-        DeviceTree.extract_surface_sparse (lattices up to 2^40 points)."""
+        DeviceTree.extract_surface_sparse (lattices up to 2^40 points).  normals: (verts, tris, normals f64 [V,3]) with
+        normals = query_gradient(verts, unit=True)[1], the field's unit gradient at every vertex."""
         if self._tree is None:
             raise HpsdfError(6, "Query on an empty octree")
         n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
+        if normals:
+            verts, tris = self.ExtractSurface(view_min, view_max, n3, iso, sparse)
+            return verts, tris, self._tree.query_gradient(verts, unit=True)[1]
         if sparse:
             return self._tree.extract_surface_sparse(view_min, view_max, n3, iso)
         return self._tree.extract_surface(view_min, view_max, n3, iso)
@@ -1064,6 +1093,18 @@ class SurfaceSparseStats(C.Structure):  # hpsdf_surface_sparse_stats, 96 bytes
 
 
 SURFACE_BLOCK = 8  # HPSDF_SURFACE_BLOCK
+GRADIENT_UNIT = 1  # HPSDF_GRADIENT_UNIT
+
+
+def query_gradient_block(block, pts, unit=False):
+    """hpsdf_query_true_gradient_block: DeviceTree.query_gradient's arrays from a serialised block on the calling thread (no device;
+    the process-wide reduction order) -> (values f64 [n], grad f64 [n,3])."""
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+    out, grad = np.empty(len(pts)), np.empty((len(pts), 3))
+    buf = bytes(block)
+    check(lib().hpsdf_query_true_gradient_block(buf, len(buf), pts.ctypes.data_as(C.c_void_p), len(pts), GRADIENT_UNIT if unit else 0,
+                                                out.ctypes.data_as(C.c_void_p), grad.ctypes.data_as(C.c_void_p)))
+    return out, grad
 
 
 def _lattice_args(lo, hi, n):
@@ -1092,11 +1133,21 @@ def surface_last_timings():
     return dict(zip(("lattice", "count", "scan", "emit", "d2h", "total"), list(out)))
 
 
-def save_obj(path, verts, tris):
+def save_obj(path, verts, tris, normals=None):
     """Writes `v` records (each vertex rounded to float32, printed with %.9g: hpsdf_obj_load reads back exactly
-    verts.astype(float32)) and 1-based `f` records."""
+    verts.astype(float32)) and 1-based `f` records.  normals (one row a vertex): `vn` records (%.9g) behind the vertices and faces as
+    `f a//a b//b c//c`, which hpsdf_obj_load reads as well."""
     v = np.asarray(verts, np.float64).reshape(-1, 3).astype(np.float32)
     t = np.asarray(tris, np.uint64).reshape(-1, 3)
+    if normals is not None:
+        vn = np.asarray(normals, np.float64).reshape(-1, 3)
+        if len(vn) != len(v):
+            raise ValueError("save_obj: one normal per vertex expected")
+        with open(path, "w") as fh:
+            fh.write("".join("v %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in v))
+            fh.write("".join("vn %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in vn))
+            fh.write("".join("f %d//%d %d//%d %d//%d\n" % (int(a) + 1, int(a) + 1, int(b) + 1, int(b) + 1, int(c) + 1, int(c) + 1) for a, b, c in t))
+        return
     with open(path, "w") as fh:
         fh.write("".join("v %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in v))
         fh.write("".join("f %d %d %d\n" % (int(a) + 1, int(b) + 1, int(c) + 1) for a, b, c in t))

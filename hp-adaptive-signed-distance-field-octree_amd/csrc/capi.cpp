@@ -1064,6 +1064,45 @@ int hpsdf_query_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double*
     HPSDF_CATCH
 }
 
+// QueryGradient (include/hpsdf.h): the value and the gradient of the polynomial it comes from (query_gradient.hip, host_query.cpp)
+int hpsdf_query_true_gradient_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz, size_t n, uint32_t flags, double* dOut,
+                                     double* dGrad) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_true_gradient: unknown flag bits");
+    if (!t || (n && (!dXyz || !dGrad))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return HPSDF_OK;
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    TreeDev td = t->dev;
+    td.leftAssoc = reductionLeftAssoc(ctx);
+    HPSDF_HIP(launchQueryTrueGradient(ctx->stream, td, ctx->dTables, dXyz, n, flags, dOut, dGrad, t->allInline));
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, uint32_t flags, double* out,
+                                   double* grad) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_true_gradient: unknown flag bits");
+    if (!t || (n && (!xyz || !grad))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return HPSDF_OK;
+    if (n <= kHostQueryPoints && smallQueriesOnHost()) {
+        if (const int hc = t->hostCopies()) return hc;
+        const int left = reductionLeftAssoc(ctx);
+        for (size_t i = 0; i < n; ++i)
+            hostQueryPointTrueGradient(*t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad + 3 * i);
+        return HPSDF_OK;
+    }
+    HostArray arr[3] = {{xyz, nullptr, n * 3 * sizeof(double)}, {nullptr, grad, n * 3 * sizeof(double)}, {nullptr, out, n * sizeof(double)}};
+    return hostCall(ctx, arr, out ? 3 : 2, [&] {
+        return hpsdf_query_true_gradient_device(ctx, t, (const double*)arr[0].dev, n, flags, out ? (double*)arr[2].dev : nullptr,
+                                                (double*)arr[1].dev);
+    });
+    HPSDF_CATCH
+}
+
 int hpsdf_query_ray_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dOrigins, const double* dDirs,
                            const double* dTMax, size_t n, uint8_t* dHit, double* dT) {
     HPSDF_TRY

@@ -33,6 +33,9 @@ hipError_t launchSlicePoints(hipStream_t stream, double c, float minX, float min
 // weighted builds: |mean FApprox| of every fit of the blocks (fit_weight_kernel)
 hipError_t launchFitWeight(hipStream_t stream, const FitBlock* dBlocks, uint32_t nBlocks, size_t ldsBytes, const FitTask* dTasks,
                            const double* dArena, double* dMeans, const DeviceTables* dTables, const uint32_t* dCount = nullptr);
+// ---- QueryGradient (query_gradient.hip): value (dOut may be null) and the polynomial's own gradient; flags: HPSDF_GRADIENT_UNIT
+hipError_t launchQueryTrueGradient(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
+                                   uint32_t flags, double* dOut, double* dGrad, bool allInline);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

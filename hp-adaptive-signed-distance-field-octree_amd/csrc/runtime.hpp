@@ -206,6 +206,9 @@ constexpr size_t kHostMeshPoints = 2;       // mesh signed distance (hpsdf_field
 double hostQueryPoint(const hpsdf_tree& t, const double* xyz);
 void hostQueryPointWithGradient(const hpsdf_tree& t, const double* xyz, double* out, double* grad, int leftAssoc);
 bool hostQueryRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, double* tOut);
+// QueryGradient of one point on the calling thread (host_query.cpp; the arithmetic is leaf_gradient.hpp's): *out (may be null) and
+// grad[0..2]; outside the root DBL_MAX and three quiet NaNs
+void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad);
 
 // innermost non-CSG field and the FieldDev the kernels take
 const hpsdf_field* innermost(const hpsdf_field* f);

@@ -303,6 +303,39 @@ HPSDF_API int hpsdf_query_gradient_device(hpsdf_ctx* ctx, const hpsdf_tree* t, c
 HPSDF_API int hpsdf_query_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, double* out,
                                         double* grad);
 
+/* ---- QueryGradient: the value and the gradient of the polynomial the value comes from (no reference counterpart).
+ * QueryWithGradient above reproduces the reference's shortcut: per axis k it differences sum_r c_r Lhat_{idx[r][k]}(u_k +- 1e-4), which
+ * leaves the other two axes' factors of every basis function out -- it is not the derivative of Query.  This call is.
+ *
+ * The arithmetic, for host and device alike (no fused multiply-add anywhere; every sum starts from 0.0 and runs in basis order):
+ *   Query's own remap (Octree.cpp:665), f32 containment test (:668) and descent (:674-701; a point on a mid-plane takes the upper
+ *   child, so on a cell face the gradient is that of the leaf Query answers from).  In the leaf -- degree p, depth d, unit coordinates
+ *   u = (pt - centre) * (2 << d) as Octree.cpp:862 -- per axis a:
+ *     L_j(u_a), j <= p      the recurrence of Query with its constants: L_0 = 1, L_j = rec[j][0] u L_{j-1} - rec[j][1] L_{j-2}
+ *     D_0 = 0, D_1 = 1, D_j = D_{j-2} + (double)(2j-1) L_{j-1}  for j >= 2      (= L_j')
+ *     LN_j = L_j nl[j][d],  DN_j = D_j nl[j][d]
+ *   value   f      Query's statements exactly: f += c_r ((LN_a(x) LN_b(y)) LN_c(z)) over rows r = (a,b,c) -- hpsdf_query_*'s bits
+ *   unit-space partials, over the same rows:
+ *     gu_0 += c_r ((DN_a(x) LN_b(y)) LN_c(z)),  gu_1 += c_r ((LN_a DN_b) LN_c),  gu_2 += c_r ((LN_a LN_b) DN_c)
+ *   world gradient  g_a = (gu_a (double)(2 << d)) rootInvSizes[a]   (the chain rule through :862 and :665; the first factor is a power
+ *     of two, the second the f32-derived reciprocal the tree holds, so anisotropic roots are handled)
+ *   HPSDF_GRADIENT_UNIT: z = g_0^2 + (g_1^2 + g_2^2), or (g_0^2 + g_1^2) + g_2^2 under hpsdf_[ctx_]set_reduction_order(1); if z > 0,
+ *     g_a = g_a / sqrt(z); otherwise the row stays as computed (zeros).
+ *   Outside the root, or a NaN coordinate: value DBL_MAX, gradient row three quiet NaNs (this call is new: it does not inherit
+ *   QueryWithGradient's "left untouched").
+ * out may be NULL (gradients only).  Unknown flag bits, a NULL grad with n > 0 or a NULL tree: HPSDF_ERR_INVALID_ARGUMENT.  n == 0 is
+ * HPSDF_OK.  _device is asynchronous on the context stream; _host answers calls of up to 32 points on the calling thread
+ * (csrc/host_query.cpp) and sends larger ones through the device; _block needs no device at all: it evaluates from a serialised
+ * block on the calling thread, under the process-wide reduction order (a malformed block: HPSDF_ERR_BAD_BLOCK).  All three give the
+ * same bits. */
+#define HPSDF_GRADIENT_UNIT 1u
+HPSDF_API int hpsdf_query_true_gradient_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_xyz, size_t n, uint32_t flags,
+                                               double* d_out, double* d_grad);
+HPSDF_API int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, uint32_t flags,
+                                             double* out, double* grad);
+HPSDF_API int hpsdf_query_true_gradient_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out,
+                                              double* grad);
+
 /* Octree::QueryRay (Octree.cpp:705-746; Ray: Include/HP/Ray.h, Source/HP/Ray.cpp:5-68) for n rays: sphere
  * tracing, <= 200 Query steps each.  hit[i] = 1/0; t[i] is written only on a hit (the reference leaves t_
  * untouched otherwise) and receives what the reference stores there -- the field value at the stopping point

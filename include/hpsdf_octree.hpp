@@ -461,6 +461,29 @@ class Octree {
         check(hpsdf_query_gradient_host(ctx_, t, xyz, n, out, grad));
     }
 
+    /// The value and the gradient of the field Query returns -- the derivative of the leaf's polynomial, which QueryWithGradient's
+    /// per-axis shortcut is not (no reference counterpart; include/hpsdf.h, "QueryGradient").  unit_: the gradient normalised.
+    /// Outside the root: DBL_MAX and three NaNs
+    f64 QueryGradient(const Eigen::Vector3d& pt_, Eigen::Vector3d& gradient_, bool unit_ = false) const {
+        const double xyz[3] = {pt_(0), pt_(1), pt_(2)};
+        double out = 0.0, g[3] = {0.0, 0.0, 0.0};
+        QueryGradient(xyz, 1, &out, g, unit_);
+        gradient_ = Eigen::Vector3d(g[0], g[1], g[2]);
+        return out;
+    }
+    /// Batched form over host arrays; out may be null (gradients only)
+    void QueryGradient(const double* xyz, usize n, double* out, double* grad, bool unit_ = false) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        check(hpsdf_query_true_gradient_host(ctx_, t, xyz, n, unit_ ? HPSDF_GRADIENT_UNIT : 0u, out, grad));
+    }
+    /// Unit normals of a mesh ExtractSurface returned: the field's unit gradient at every vertex, 3 doubles a vertex
+    std::vector<double> SurfaceNormals(const SurfaceMesh& mesh_) const {
+        std::vector<double> normals(mesh_.vertices.size());
+        if (!normals.empty()) QueryGradient(mesh_.vertices.data(), mesh_.vertices.size() / 3, nullptr, normals.data(), true);
+        return normals;
+    }
+
     /// Sphere tracing along ray_ (<= 200 Query steps).  As in the reference (Octree.cpp:705-746), t_ receives
     /// the field value at the stopping point on a hit and is left untouched otherwise   (Octree.h:75)
     bool QueryRay(const Ray& ray_, const f64 tMax_, f64& t_) const {
