@@ -155,6 +155,14 @@ _SIGNATURES = {
     "hpsdf_query_true_gradient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "hpsdf_query_true_gradient_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "hpsdf_query_true_gradient_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "hpsdf_project_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_project_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_project_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_surface_project_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                                 C.c_uint32, C.POINTER(C.c_uint64)]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -604,6 +612,39 @@ class DeviceTree:
         check(lib().hpsdf_query_true_gradient_device(self.ctx.handle, self.handle, C.c_void_p(d_xyz_ptr), n, GRADIENT_UNIT if unit else 0,
                                                      C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(d_grad_ptr)))
 
+    def project(self, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
+        """ProjectToSurface (include/hpsdf.h): Newton's iteration along the gradient onto {Query = iso}, per point until |f - iso| <= tol
+        -> (points f64 [n,3], values f64 [n], grad f64 [n,3], iters u8 [n], status u8 [n]); (values, grad) is query_gradient(points, unit)
+        bit for bit.  status: PROJECT_CONVERGED, PROJECT_ITER_LIMIT (max_iter steps taken: the iteration can hop between two cells for
+        ever near creases), PROJECT_LEFT_ROOT (DBL_MAX, NaN row), PROJECT_FLAT (zero gradient)."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = len(pts)
+        out, val, grad = np.empty((n, 3)), np.empty(n), np.empty((n, 3))
+        iters, status = np.empty(n, np.uint8), np.empty(n, np.uint8)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().hpsdf_project_host(self.ctx.handle, self.handle, vp(pts), n, float(iso), float(tol), _max_iter(max_iter),
+                                       PROJECT_UNIT if unit else 0, vp(out), vp(val), vp(grad), vp(iters), vp(status)))
+        return out, val, grad, iters, status
+
+    def project_device(self, d_xyz_ptr, n, d_out_xyz_ptr, d_out_val_ptr=0, d_out_grad_ptr=0, d_out_iters_ptr=0, d_out_status_ptr=0, iso=0.0,
+                       tol=1e-9, max_iter=16, unit=False):
+        """Raw device pointers (ints; 0 = NULL for every output but d_out_xyz_ptr, which may equal d_xyz_ptr); asynchronous on the
+        context stream."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        check(lib().hpsdf_project_device(self.ctx.handle, self.handle, vp(d_xyz_ptr), n, float(iso), float(tol), _max_iter(max_iter),
+                                         PROJECT_UNIT if unit else 0, vp(d_out_xyz_ptr), vp(d_out_val_ptr), vp(d_out_grad_ptr),
+                                         vp(d_out_iters_ptr), vp(d_out_status_ptr)))
+
+    def project_vertices(self, verts, h, iso=0.0, tol=1e-9, max_iter=16):
+        """hpsdf_surface_project_vertices: the vertices of an extracted mesh moved onto the level set, each only if its projection
+        converged and stays within half a cube (h[a] / 2 per axis) of it -> (verts f64 [V,3] (a copy), n_moved)."""
+        v = np.array(verts, np.float64).reshape(-1, 3)
+        h3 = (C.c_double * 3)(*[float(x) for x in h])
+        moved = C.c_uint64()
+        check(lib().hpsdf_surface_project_vertices(self.ctx.handle, self.handle, v.ctypes.data_as(C.c_void_p), len(v), h3, float(iso),
+                                                   float(tol), _max_iter(max_iter), C.byref(moved)))
+        return v, int(moved.value)
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1021,6 +1062,15 @@ class Octree:
         out, grad = self._tree.query_gradient(a, unit)
         return (float(out[0]), grad[0]) if a.ndim == 1 else (out, grad)
 
+    def ProjectToSurface(self, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
+        """The points moved onto the level set {Query = iso} along the gradient (DeviceTree.project): one point (3,) -> (point (3,),
+        value, grad (3,), iters, status) with scalars, or (n,3) -> the five arrays."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        a = np.asarray(pts, np.float64)
+        out, val, grad, iters, status = self._tree.project(a, iso, tol, max_iter, unit)
+        return (out[0], float(val[0]), grad[0], int(iters[0]), int(status[0])) if a.ndim == 1 else (out, val, grad, iters, status)
+
     def QueryRay(self, origins, directions, t_max):
         """Octree::QueryRay (Octree.h:75) for one ray -> (hit, t) or (n,3) arrays -> (hit[n], t[n])."""
         if self._tree is None:
@@ -1038,20 +1088,26 @@ class Octree:
         write_bmp(fname + ".bmp", rgb)
         return rgb
 
-    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False, normals=False):
+    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False, normals=False, project=False, tol=1e-9, max_iter=16):
         """Triangle mesh of the level set {Query = iso} over the box [view_min, view_max] with n cubes per axis (an int or three)
         -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice.  sparse: the same arrays through
-        DeviceTree.extract_surface_sparse (lattices up to 2^40 points).  normals: (verts, tris, normals f64 [V,3]) with
-        normals = query_gradient(verts, unit=True)[1], the field's unit gradient at every vertex."""
+        DeviceTree.extract_surface_sparse (lattices up to 2^40 points).  project: the vertices -- linear interpolants along lattice
+        edges -- are moved onto the polynomial's level set (DeviceTree.project_vertices with tol and max_iter: a vertex moves only if
+        its projection converged within half a cube of it); tris is unchanged.  normals: (verts, tris, normals f64 [V,3]) with
+        normals = query_gradient(verts, unit=True)[1], the field's unit gradient at every vertex (the projected ones under project)."""
         if self._tree is None:
             raise HpsdfError(6, "Query on an empty octree")
         n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
         if normals:
-            verts, tris = self.ExtractSurface(view_min, view_max, n3, iso, sparse)
+            verts, tris = self.ExtractSurface(view_min, view_max, n3, iso, sparse, False, project, tol, max_iter)
             return verts, tris, self._tree.query_gradient(verts, unit=True)[1]
         if sparse:
-            return self._tree.extract_surface_sparse(view_min, view_max, n3, iso)
-        return self._tree.extract_surface(view_min, view_max, n3, iso)
+            verts, tris = self._tree.extract_surface_sparse(view_min, view_max, n3, iso)
+        else:
+            verts, tris = self._tree.extract_surface(view_min, view_max, n3, iso)
+        if project:
+            verts = self._tree.project_vertices(verts, surface_cube_size(view_min, view_max, n3), iso, tol, max_iter)[0]
+        return verts, tris
 
     def GetRootAABB(self):
         return self.config.root_min, self.config.root_max
@@ -1094,6 +1150,34 @@ class SurfaceSparseStats(C.Structure):  # hpsdf_surface_sparse_stats, 96 bytes
 
 SURFACE_BLOCK = 8  # HPSDF_SURFACE_BLOCK
 GRADIENT_UNIT = 1  # HPSDF_GRADIENT_UNIT
+PROJECT_UNIT = 1  # HPSDF_PROJECT_UNIT
+PROJECT_CONVERGED, PROJECT_ITER_LIMIT, PROJECT_LEFT_ROOT, PROJECT_FLAT = 0, 1, 2, 3  # HPSDF_PROJECT_*: out_status
+
+
+def _max_iter(max_iter):
+    m = int(max_iter)
+    if m < 0:
+        raise ValueError("max_iter must be >= 0")
+    return min(m, 0xFFFFFFFF)  # (the library rejects anything above 255)
+
+
+def surface_cube_size(lo, hi, n):
+    """The cube size h[a] = (hi[a] - lo[a]) / n[a] of hpsdf_extract_surface's lattice, as the library derives it (doubles)."""
+    return tuple((float(hi[a]) - float(lo[a])) / float(int(n[a])) for a in range(3))
+
+
+def project_block(block, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
+    """hpsdf_project_block: DeviceTree.project's arrays from a serialised block on the calling thread (no device; the process-wide
+    reduction order) -> (points f64 [n,3], values f64 [n], grad f64 [n,3], iters u8 [n], status u8 [n])."""
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+    n = len(pts)
+    out, val, grad = np.empty((n, 3)), np.empty(n), np.empty((n, 3))
+    iters, status = np.empty(n, np.uint8), np.empty(n, np.uint8)
+    buf = bytes(block)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().hpsdf_project_block(buf, len(buf), vp(pts), n, float(iso), float(tol), _max_iter(max_iter), PROJECT_UNIT if unit else 0,
+                                    vp(out), vp(val), vp(grad), vp(iters), vp(status)))
+    return out, val, grad, iters, status
 
 
 def query_gradient_block(block, pts, unit=False):

@@ -1103,6 +1103,85 @@ int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const do
     HPSDF_CATCH
 }
 
+// ProjectToSurface (include/hpsdf.h): Newton's iteration onto {Query = iso} (project.hip, host_query.cpp)
+int hpsdf_project_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz, size_t n, double iso, double tol, uint32_t maxIter,
+                         uint32_t flags, double* dOutXyz, double* dOutVal, double* dOutGrad, uint8_t* dOutIters, uint8_t* dOutStatus) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = projectArgumentError(flags, iso, tol, maxIter)) return rc;
+    if (!t || (n && (!dXyz || !dOutXyz))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return HPSDF_OK;
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    TreeDev td = t->dev;
+    td.leftAssoc = reductionLeftAssoc(ctx);
+    HPSDF_HIP(launchProject(ctx->stream, td, ctx->dTables, dXyz, n, ProjectArgs{iso, tol, maxIter, flags}, dOutXyz, dOutVal, dOutGrad,
+                            dOutIters, dOutStatus));
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+int hpsdf_project_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, double iso, double tol, uint32_t maxIter,
+                       uint32_t flags, double* outXyz, double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = projectArgumentError(flags, iso, tol, maxIter)) return rc;
+    if (!t || (n && (!xyz || !outXyz))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return HPSDF_OK;
+    if (n <= kHostQueryPoints && smallQueriesOnHost()) {
+        if (const int hc = t->hostCopies()) return hc;
+        const int left = reductionLeftAssoc(ctx);
+        for (size_t i = 0; i < n; ++i)
+            hostProjectPoint(*t, xyz + 3 * i, iso, tol, maxIter, (flags & HPSDF_PROJECT_UNIT) != 0u, left, outXyz + 3 * i,
+                             outVal ? outVal + i : nullptr, outGrad ? outGrad + 3 * i : nullptr, outIters ? outIters + i : nullptr,
+                             outStatus ? outStatus + i : nullptr);
+        return HPSDF_OK;
+    }
+    // the input and the point output have device arrays of their own (outXyz may be xyz); the optional outputs follow, those asked for
+    HostArray arr[6] = {{xyz, nullptr, n * 3 * sizeof(double)}, {nullptr, outXyz, n * 3 * sizeof(double)}};
+    int used = 2, iVal = -1, iGrad = -1, iIters = -1, iStatus = -1;
+    if (outVal) arr[iVal = used++] = HostArray{nullptr, outVal, n * sizeof(double)};
+    if (outGrad) arr[iGrad = used++] = HostArray{nullptr, outGrad, n * 3 * sizeof(double)};
+    if (outIters) arr[iIters = used++] = HostArray{nullptr, outIters, n};
+    if (outStatus) arr[iStatus = used++] = HostArray{nullptr, outStatus, n};
+    return hostCall(ctx, arr, used, [&] {
+        return hpsdf_project_device(ctx, t, (const double*)arr[0].dev, n, iso, tol, maxIter, flags, (double*)arr[1].dev,
+                                    iVal < 0 ? nullptr : (double*)arr[iVal].dev, iGrad < 0 ? nullptr : (double*)arr[iGrad].dev,
+                                    iIters < 0 ? nullptr : (uint8_t*)arr[iIters].dev, iStatus < 0 ? nullptr : (uint8_t*)arr[iStatus].dev);
+    });
+    HPSDF_CATCH
+}
+
+int hpsdf_surface_project_vertices(hpsdf_ctx* ctx, const hpsdf_tree* t, double* verts, uint64_t nv, const double h[3], double iso,
+                                   double tol, uint32_t maxIter, uint64_t* nMoved) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = projectArgumentError(0u, iso, tol, maxIter)) return rc;
+    if (!t || (nv && !verts) || !h) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    for (int a = 0; a < 3; ++a)
+        if (!(h[a] >= 0.0)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_surface_project_vertices: h must be >= 0 on every axis");
+    if (nMoved) *nMoved = 0;
+    if (nv == 0) return HPSDF_OK;
+    std::vector<double> moved(3 * (size_t)nv);
+    std::vector<uint8_t> status((size_t)nv);
+    if (const int rc = hpsdf_project_host(ctx, t, verts, (size_t)nv, iso, tol, maxIter, 0u, moved.data(), nullptr, nullptr, nullptr, status.data()))
+        return rc;
+    uint64_t count = 0;
+    for (size_t i = 0; i < (size_t)nv; ++i) {
+        const double* m = &moved[3 * i];
+        double* v = verts + 3 * i;
+        // a converged projection that stays within half a cube of the vertex on every axis; anything else leaves the vertex as it was
+        if (status[i] == HPSDF_PROJECT_CONVERGED && std::fabs(m[0] - v[0]) <= 0.5 * h[0] && std::fabs(m[1] - v[1]) <= 0.5 * h[1] &&
+            std::fabs(m[2] - v[2]) <= 0.5 * h[2]) {
+            v[0] = m[0], v[1] = m[1], v[2] = m[2];
+            ++count;
+        }
+    }
+    if (nMoved) *nMoved = count;
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
 int hpsdf_query_ray_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dOrigins, const double* dDirs,
                            const double* dTMax, size_t n, uint8_t* dHit, double* dT) {
     HPSDF_TRY

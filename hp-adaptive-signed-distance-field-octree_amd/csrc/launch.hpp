@@ -36,6 +36,14 @@ hipError_t launchFitWeight(hipStream_t stream, const FitBlock* dBlocks, uint32_t
 // ---- QueryGradient (query_gradient.hip): value (dOut may be null) and the polynomial's own gradient; flags: HPSDF_GRADIENT_UNIT
 hipError_t launchQueryTrueGradient(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
                                    uint32_t flags, double* dOut, double* dGrad, bool allInline);
+// ---- ProjectToSurface (project.hip): Newton's iteration onto {Query = iso}; dOutXyz may be dXyz, the other outputs may be null
+struct ProjectArgs {
+    double iso, tol;
+    uint32_t maxIter;  // <= 255
+    uint32_t flags;    // HPSDF_PROJECT_UNIT
+};
+hipError_t launchProject(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n, const ProjectArgs& a,
+                         double* dOutXyz, double* dOutVal, double* dOutGrad, uint8_t* dOutIters, uint8_t* dOutStatus);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -65,6 +66,36 @@ __host__ __device__ inline void finishTrueGradient(const double (&gu)[3], int de
             g[0] = g[0] / nrm, g[1] = g[1] / nrm, g[2] = g[2] / nrm;
         }
     }
+}
+
+// finishTrueGradient's normalisation on its own, for a world gradient that already went through it with unit = false
+__host__ __device__ inline void unitGradient(double (&g)[3], int leftAssoc) {
+    const double a = g[0] * g[0], b = g[1] * g[1], c = g[2] * g[2];
+    const double z = leftAssoc ? (a + b) + c : a + (b + c);
+    if (z > 0.0) {
+        const double nrm = sqrt(z);
+        g[0] = g[0] / nrm, g[1] = g[1] / nrm, g[2] = g[2] / nrm;
+    }
+}
+
+// One turn of ProjectToSurface's loop (include/hpsdf.h, "ProjectToSurface") after (f, g) = QueryGradient(x) with the world gradient:
+// the stopping tests in their stated order, then the Newton step along g.  Returns the HPSDF_PROJECT_* status the point stops with, or
+// -1 after x has moved (the caller counts the step).  One set of statements for the calling thread (host_query.cpp) and the kernels
+// (project.hip).
+__host__ __device__ inline int projectStep(double f, const double (&g)[3], double iso, double tol, uint32_t k, uint32_t maxIter,
+                                           int leftAssoc, double (&x)[3]) {
+    if (f == DBL_MAX) return 2;  // HPSDF_PROJECT_LEFT_ROOT
+    const double r = f - iso;
+    if (fabs(r) <= tol) return 0;  // HPSDF_PROJECT_CONVERGED
+    const double a = g[0] * g[0], b = g[1] * g[1], c = g[2] * g[2];
+    const double z = leftAssoc ? (a + b) + c : a + (b + c);
+    if (!(z > 0.0)) return 3;    // HPSDF_PROJECT_FLAT
+    if (k == maxIter) return 1;  // HPSDF_PROJECT_ITER_LIMIT
+    const double s = r / z;
+    x[0] = x[0] - s * g[0];
+    x[1] = x[1] - s * g[1];
+    x[2] = x[2] - s * g[2];
+    return -1;
 }
 
 }  // namespace hpsdf

@@ -6,6 +6,7 @@
 //                                    the wave fetches the points' 128-byte lines cooperatively into LDS, as query_kernel does;
 //   query_true_gradient_kernel<MAXP> any tree: queryPoint's descent (top table, then the walk), the leaf's coefficients lane by lane;
 //   query_true_gradient_few_kernel   the same for a handful of points in workgroups of one wave.
+// The per-point routine of the last two, trueGradientPoint, lives in true_gradient_point.hpp (project.hip runs it too).
 // Rows of points outside the root (or with a NaN coordinate) are DBL_MAX and three quiet NaNs.
 //
 // Built with -ffp-contract=off like every other unit: the host versions (host_query.cpp) give the same bits.
@@ -18,90 +19,17 @@
 #include "launch.hpp"
 #include "leaf_eval.hpp"
 #include "leaf_gradient.hpp"
+#include "true_gradient_point.hpp"
 
 namespace hpsdf {
 
 namespace {
-
-__device__ __forceinline__ double quietNaN() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 __device__ __forceinline__ void storeGradientRow(size_t i, double f, const double (&g)[3], double* __restrict__ out, double* __restrict__ grad) {
     if (out != nullptr) __builtin_nontemporal_store(f, &out[i]);
     __builtin_nontemporal_store(g[0], &grad[3 * i]);
     __builtin_nontemporal_store(g[1], &grad[3 * i + 1]);
     __builtin_nontemporal_store(g[2], &grad[3 * i + 2]);
-}
-
-// One point through the tree: queryPoint's statements (leaf_eval.hpp) down to the leaf, then value and gradient.
-template <int MAXP>
-__device__ __forceinline__ double trueGradientPoint(const TreeDev& t, double x, double y, double z, bool unit, const double* sNl,
-                                                    const double* sRec, double (&g)[3]) {
-    // Octree.cpp:665
-    const double px = (x - t.rootCentre[0]) * t.rootInvSizes[0];
-    const double py = (y - t.rootCentre[1]) * t.rootInvSizes[1];
-    const double pz = (z - t.rootCentre[2]) * t.rootInvSizes[2];
-    // :668 containment on the f32 cast, both ends inclusive; NaN fails
-    const float fx = (float)px, fy = (float)py, fz = (float)pz;
-    if (!(fx >= -0.5f && fx <= 0.5f && fy >= -0.5f && fy <= 0.5f && fz >= -0.5f && fz <= 0.5f)) {
-        g[0] = g[1] = g[2] = quietNaN();
-        return DBL_MAX;
-    }
-    // :674-701, the complete levels by comparison alone (>= takes the upper child), then one table lookup
-    double cx = 0.0, cy = 0.0, cz = 0.0, q = 0.25;
-    uint32_t ix = 0, iy = 0, iz = 0;
-    int depth = 0;
-    for (; depth < t.topDepth; ++depth) {
-        const bool ux = px >= cx, uy = py >= cy, uz = pz >= cz;
-        ix = ix * 2u + (ux ? 1u : 0u);
-        iy = iy * 2u + (uy ? 1u : 0u);
-        iz = iz * 2u + (uz ? 1u : 0u);
-        cx = ux ? cx + q : cx - q;
-        cy = uy ? cy + q : cy - q;
-        cz = uz ? cz + q : cz - q;
-        q = q * 0.5;
-    }
-    const uint32_t code = ix + ((iy + (iz << t.topDepth)) << t.topDepth);
-    // the top entry's line: the record and, for a leaf of degree <= 2, its coefficients (issued together)
-    const TopEntry* __restrict__ e = t.top + code;
-    const uint2 hdr = *reinterpret_cast<const uint2*>(e);
-    double cv[10];
-    {
-        const double2* __restrict__ c2 = reinterpret_cast<const double2*>(e->c);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const double2 v = c2[i];
-            cv[2 * i] = v.x;
-            cv[2 * i + 1] = v.y;
-        }
-    }
-    NodeRec rec{hdr.x, hdr.y};
-    double f, gu[3];
-    if (rec.b <= 2u) {
-        const double s = (double)(2 << depth);  // :862
-        const double u[3] = {(px - cx) * s, (py - cy) * s, (pz - cz) * s};
-        if (rec.b == 2u)
-            f = leafTrueGradientVals<2>(cv, u, depth, sNl, sRec, gu);
-        else if (rec.b == 1u)
-            f = leafTrueGradientVals<1>(cv, u, depth, sNl, sRec, gu);
-        else
-            f = leafTrueGradientVals<0>(cv, u, depth, sNl, sRec, gu);
-    } else {
-        while (rec.b == kInteriorTag) {
-            const bool ux = px >= cx, uy = py >= cy, uz = pz >= cz;
-            const uint32_t idx = rec.a + (ux ? 1u : 0u) + (uy ? 2u : 0u) + (uz ? 4u : 0u);
-            cx = ux ? cx + q : cx - q;
-            cy = uy ? cy + q : cy - q;
-            cz = uz ? cz + q : cz - q;
-            q = q * 0.5;
-            ++depth;
-            rec = t.nodes[idx];
-        }
-        const double s = (double)(2 << depth);  // :862
-        const double u[3] = {(px - cx) * s, (py - cy) * s, (pz - cz) * s};
-        f = leafTrueGradientOf<MAXP>(t.coeffs + rec.a, (int)rec.b, u, depth, sNl, sRec, gu);
-    }
-    finishTrueGradient(gu, depth, t.rootInvSizes, unit, t.leftAssoc, g);
-    return f;
 }
 
 }  // namespace

@@ -209,6 +209,11 @@ bool hostQueryRay(const hpsdf_tree& t, const double* origin, const double* dir, 
 // QueryGradient of one point on the calling thread (host_query.cpp; the arithmetic is leaf_gradient.hpp's): *out (may be null) and
 // grad[0..2]; outside the root DBL_MAX and three quiet NaNs
 void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad);
+// ProjectToSurface of one point on the calling thread (host_query.cpp): the kernels' rows bit for bit; every output but outXyz may be
+// null, outXyz may be xyz.  projectArgumentError: the argument checks the three hpsdf_project_* entries share (sets the message)
+void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc, double* outXyz,
+                      double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus);
+int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter);
 
 // innermost non-CSG field and the FieldDev the kernels take
 const hpsdf_field* innermost(const hpsdf_field* f);

@@ -336,6 +336,55 @@ HPSDF_API int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t
 HPSDF_API int hpsdf_query_true_gradient_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out,
                                               double* grad);
 
+/* ---- ProjectToSurface: Newton's iteration along the gradient onto the level set {Query = iso} (no reference counterpart).
+ * Per point, with iso finite, tol >= 0 (not NaN) and max_iter in 0..255; host, device and block entries run the same statements (no
+ * fused multiply-add anywhere) and give the same bits:
+ *     x = input point;  k = 0
+ *     loop:
+ *       (f, g) = QueryGradient(x), the world gradient, not normalised -- the statements stated above
+ *       if f == DBL_MAX (x outside the root, or a NaN coordinate):   status = HPSDF_PROJECT_LEFT_ROOT;   stop
+ *       r = f - iso
+ *       if fabs(r) <= tol:                                           status = HPSDF_PROJECT_CONVERGED;   stop
+ *       a = g_0 g_0, b = g_1 g_1, c = g_2 g_2;  z = a + (b + c), or (a + b) + c under hpsdf_[ctx_]set_reduction_order(1)
+ *       if !(z > 0):                                                 status = HPSDF_PROJECT_FLAT;        stop
+ *       if k == max_iter:                                            status = HPSDF_PROJECT_ITER_LIMIT;  stop
+ *       s = r / z;   x_a = x_a - s g_a  (a = 0, 1, 2);   k = k + 1
+ * Outputs per point, every one except out_xyz optional (NULL):
+ *   out_xyz[3]   the x at which the loop stopped (LEFT_ROOT: the position outside the root; a NaN input: the input as it is)
+ *   out_val      f there;   out_grad[3]  g there, normalised as HPSDF_GRADIENT_UNIT normalises it under HPSDF_PROJECT_UNIT; three quiet
+ *                NaNs for LEFT_ROOT.  Hence (out_val, out_grad) is QueryGradient(out_xyz) bit for bit on every row.
+ *   out_iters    k (uint8_t);   out_status  the status (uint8_t)
+ * out_xyz may be the input array itself (a point is read before its row is written).
+ * There is no damping, no step clamp and no line search, and the result is where the gradient lines lead, not a guaranteed closest
+ * point.  The field is piecewise polynomial and discontinuous across cell faces: near creases and the medial axis the iteration can
+ * hop between two cells for ever, each cell's polynomial sending the point back into the other.  HPSDF_PROJECT_ITER_LIMIT reports
+ * that (or a max_iter too small); the row then holds the last position reached.  (A step that overflows can produce a NaN coordinate;
+ * the next turn stops with LEFT_ROOT, and the bits of such a NaN are the platform's.)
+ * Unknown flag bits, a NULL out_xyz (or input) with n > 0, a NULL tree, tol negative or NaN, a non-finite iso, max_iter > 255:
+ * HPSDF_ERR_INVALID_ARGUMENT, and no output is written.  n == 0 is HPSDF_OK.  _device is asynchronous on the context stream; _host
+ * answers calls of up to 32 points on the calling thread and sends larger ones through the device; _block needs no device: it works
+ * from a serialised block on the calling thread under the process-wide reduction order (a malformed block: HPSDF_ERR_BAD_BLOCK). */
+#define HPSDF_PROJECT_UNIT 1u
+enum { HPSDF_PROJECT_CONVERGED = 0, HPSDF_PROJECT_ITER_LIMIT = 1, HPSDF_PROJECT_LEFT_ROOT = 2, HPSDF_PROJECT_FLAT = 3 };
+HPSDF_API int hpsdf_project_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_xyz, size_t n, double iso, double tol,
+                                   uint32_t max_iter, uint32_t flags, double* d_out_xyz, double* d_out_val, double* d_out_grad,
+                                   uint8_t* d_out_iters, uint8_t* d_out_status);
+HPSDF_API int hpsdf_project_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, double iso, double tol, uint32_t max_iter,
+                                 uint32_t flags, double* out_xyz, double* out_val, double* out_grad, uint8_t* out_iters,
+                                 uint8_t* out_status);
+HPSDF_API int hpsdf_project_block(const void* block, size_t size, const double* xyz, size_t n, double iso, double tol, uint32_t max_iter,
+                                  uint32_t flags, double* out_xyz, double* out_val, double* out_grad, uint8_t* out_iters,
+                                  uint8_t* out_status);
+/* Marching-cubes vertices are linear interpolants along lattice edges and do not lie on the polynomial's level set.  This call moves
+ * the nv vertices of verts (host, 3 doubles each, in place) onto it: every vertex goes through hpsdf_project_host (flags 0), and vertex
+ * i is replaced by its projection only if its status is HPSDF_PROJECT_CONVERGED and fabs(projected_a - vertex_a) <= 0.5 * h[a] on every
+ * axis a, h being the cube size of the lattice the mesh was extracted on ((hi[a] - lo[a]) / n[a] of hpsdf_extract_surface).  Any other
+ * vertex stays exactly as it was, so the triangle list stays valid and no vertex moves far enough to fold its triangles.  *n_moved
+ * (may be NULL): how many vertices were replaced.  A NULL verts with nv > 0, a NULL h or an h[a] that is negative or NaN, and
+ * whatever hpsdf_project_host rejects: HPSDF_ERR_INVALID_ARGUMENT, verts untouched. */
+HPSDF_API int hpsdf_surface_project_vertices(hpsdf_ctx* ctx, const hpsdf_tree* t, double* verts, uint64_t nv, const double h[3], double iso,
+                                             double tol, uint32_t max_iter, uint64_t* n_moved);
+
 /* Octree::QueryRay (Octree.cpp:705-746; Ray: Include/HP/Ray.h, Source/HP/Ray.cpp:5-68) for n rays: sphere
  * tracing, <= 200 Query steps each.  hit[i] = 1/0; t[i] is written only on a hit (the reference leaves t_
  * untouched otherwise) and receives what the reference stores there -- the field value at the stopping point

@@ -563,6 +563,48 @@ class Octree {
         return m;
     }
 
+    /// Moves pt_ onto the level set {Query = iso_} by Newton's iteration along the gradient, until |Query - iso_| <= tol_ or maxIter_
+    /// steps (no reference counterpart; include/hpsdf.h, "ProjectToSurface").  Returns the status: HPSDF_PROJECT_CONVERGED,
+    /// _ITER_LIMIT (near creases the iteration can hop between two cells for ever), _LEFT_ROOT or _FLAT; projected_ is where it stopped.
+    /// value_, gradient_ (QueryGradient there; unit_: normalised) and iters_ are optional
+    int ProjectToSurface(const Eigen::Vector3d& pt_, Eigen::Vector3d& projected_, f64 iso_ = 0.0, f64 tol_ = 1e-9, uint32_t maxIter_ = 16,
+                         f64* value_ = nullptr, Eigen::Vector3d* gradient_ = nullptr, bool unit_ = false, uint32_t* iters_ = nullptr) const {
+        const double xyz[3] = {pt_(0), pt_(1), pt_(2)};
+        double out[3] = {0.0, 0.0, 0.0}, val = 0.0, g[3] = {0.0, 0.0, 0.0};
+        uint8_t it = 0, st = 0;
+        ProjectToSurface(xyz, 1, out, iso_, tol_, maxIter_, &val, g, &it, &st, unit_);
+        projected_ = Eigen::Vector3d(out[0], out[1], out[2]);
+        if (value_) *value_ = val;
+        if (gradient_) *gradient_ = Eigen::Vector3d(g[0], g[1], g[2]);
+        if (iters_) *iters_ = it;
+        return st;
+    }
+    /// Batched form over host arrays; outXyz may be xyz, every other output may be null
+    void ProjectToSurface(const double* xyz, usize n, double* outXyz, f64 iso_ = 0.0, f64 tol_ = 1e-9, uint32_t maxIter_ = 16,
+                          double* outVal = nullptr, double* outGrad = nullptr, uint8_t* outIters = nullptr, uint8_t* outStatus = nullptr,
+                          bool unit_ = false) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        check(hpsdf_project_host(ctx_, t, xyz, n, iso_, tol_, maxIter_, unit_ ? HPSDF_PROJECT_UNIT : 0u, outXyz, outVal, outGrad, outIters,
+                                 outStatus));
+    }
+    /// Moves the vertices of a mesh ExtractSurface(area_, resolution_, iso_) returned onto the level set, in place: a vertex is replaced
+    /// by its projection only if that converged within half a cube of it on every axis (hpsdf_surface_project_vertices), so the
+    /// triangles stay as they are.  Returns how many vertices were replaced
+    u64 ProjectSurface(SurfaceMesh& mesh_, const Eigen::AlignedBox3f& area_, const Eigen::Vector3i& resolution_, f64 iso_ = 0.0,
+                       f64 tol_ = 1e-9, uint32_t maxIter_ = 16) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        double h[3];
+        for (int a = 0; a < 3; ++a) {
+            if (resolution_(a) < 1) throw Error(HPSDF_ERR_INVALID_ARGUMENT, "resolution must be at least 1 per axis");
+            h[a] = ((double)area_.max()(a) - (double)area_.min()(a)) / (double)(uint32_t)resolution_(a);  // hpsdf_extract_surface's h
+        }
+        uint64_t moved = 0;
+        check(hpsdf_surface_project_vertices(ctx_, t, mesh_.vertices.data(), mesh_.vertices.size() / 3, h, iso_, tol_, maxIter_, &moved));
+        return moved;
+    }
+
     /// Returns the aabb of the root node   (Octree.h:81)
     Eigen::AlignedBox3f GetRootAABB() const { return config_.root; }
 
