@@ -1,8 +1,9 @@
 // Structural validation of a serialised MemoryBlock's node array (Octree::ToMemoryBlock layout, Octree.cpp:424-456).
 //
 // The reference's FromMemoryBlock (Octree.cpp:403-421) trusts its input; the entry points here take bytes from
-// anywhere (files, other processes), so both deserialisers -- hpsdf_tree_upload and the continuity post-process --
-// walk the tree from the root with these checks before anything indexes by what the block says:
+// anywhere (files, other processes), so every deserialiser -- mirrorBlock (block.hpp: hpsdf_tree_upload and the *_block
+// entry points) and the continuity post-process -- walks the tree from the root with these checks before anything
+// indexes by what the block says:
 //   * an interior node's 8 children lie inside the node array (compared without wrap-around) and behind the root;
 //   * every node is reached at most once (no cycles, no shared sub-trees): the walk terminates in <= nNodes steps;
 //   * the path length never exceeds TREE_MAX_DEPTH + 1 and equals the leaf's stored depth;

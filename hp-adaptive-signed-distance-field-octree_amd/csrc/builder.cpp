@@ -8,6 +8,7 @@
 #include <cstring>
 #include <thread>
 
+#include "block.hpp"
 #include "launch.hpp"
 
 using namespace hpsdf;
@@ -946,12 +947,12 @@ int builderPackHost(hpsdf_build* b, hpsdf_ctx* ctx, double* out) {
 //   [u64 nCoeffs][f64 x nCoeffs][u64 nNodes][Node x nNodes][Config], malloc-owned
 int builderAssemble(hpsdf_build* b, const double* const* packs, void** block, size_t* size) {
     if (!b->laidOut) return fail(HPSDF_ERR_STATE, "call hpsdf_build_layout first");
-    const size_t bytes = 8 + 8 * (size_t)b->nCoeffsTotal + 8 + sizeof(hpsdf_node) * b->nodes.size() + sizeof(hpsdf_config);
+    const uint64_t nc = b->nCoeffsTotal, nn = b->nodes.size();
+    const size_t bytes = blockBytes(nc, nn);
     uint8_t* p = (uint8_t*)std::malloc(bytes);
     if (!p) return fail(HPSDF_ERR_OUT_OF_MEMORY, "malloc of the memory block failed");
-    const uint64_t nc = b->nCoeffsTotal, nn = b->nodes.size();
     std::memcpy(p, &nc, 8);
-    double* store = (double*)(p + 8);
+    double* store = (double*)(p + kBlockCoeffsAt);
     std::memset(store, 0, 8 * (size_t)nc);
     std::vector<uint64_t> cur(b->world, 0);
     for (const auto& l : b->layout) {
@@ -962,10 +963,9 @@ int builderAssemble(hpsdf_build* b, const double* const* packs, void** block, si
         std::memcpy(store + l.dst, packs[l.owner] + cur[l.owner], l.count * sizeof(double));
         cur[l.owner] += l.count;
     }
-    uint8_t* q = p + 8 + 8 * (size_t)nc;
-    std::memcpy(q, &nn, 8);
-    std::memcpy(q + 8, b->nodes.data(), sizeof(hpsdf_node) * b->nodes.size());
-    std::memcpy(q + 8 + sizeof(hpsdf_node) * b->nodes.size(), &b->cfg, sizeof(hpsdf_config));
+    std::memcpy(p + blockNodeCountAt(nc), &nn, 8);
+    std::memcpy(p + blockNodesAt(nc), b->nodes.data(), sizeof(hpsdf_node) * b->nodes.size());
+    std::memcpy(p + blockConfigAt(nc, nn), &b->cfg, sizeof(hpsdf_config));
     *block = p;
     *size = bytes;
     return HPSDF_OK;

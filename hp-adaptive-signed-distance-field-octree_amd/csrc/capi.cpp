@@ -19,7 +19,7 @@
 #include "builder.hpp"
 #include "continuity.hpp"
 #include "frontier.hpp"
-#include "block_check.hpp"
+#include "block.hpp"
 #include "launch.hpp"
 #include "runtime.hpp"
 
@@ -242,17 +242,6 @@ int hostCall(hpsdf_ctx* ctx, HostArray* arrays, int nArrays, Run&& run) {
     return HPSDF_OK;
 }
 }  // namespace
-
-#define HPSDF_TRY                                                            \
-    try {
-#define HPSDF_CATCH                                                          \
-    }                                                                        \
-    catch (const std::bad_alloc&) {                                          \
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");      \
-    }                                                                        \
-    catch (const std::exception& ex) {                                       \
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what()); \
-    }
 
 extern "C" {
 
@@ -828,64 +817,17 @@ int hpsdf_tree_upload(hpsdf_ctx* ctx, const void* block, size_t size, hpsdf_tree
     if (!out) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null out");
     *out = nullptr;
     if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "trees are queried on the GPU: a device context is required");
-    if (!block || size < 16 + sizeof(hpsdf_config)) return fail(HPSDF_ERR_BAD_BLOCK, "block too small");
-    const uint8_t* p = (const uint8_t*)block;
-    uint64_t nCoeffs, nNodes;
-    std::memcpy(&nCoeffs, p, 8);
-    if (nCoeffs > (size - 16 - sizeof(hpsdf_config)) / 8) return fail(HPSDF_ERR_BAD_BLOCK, "coefficient count exceeds block");
-    const double* coeffs = (const double*)(p + 8);
-    std::memcpy(&nNodes, p + 8 + 8 * nCoeffs, 8);
-    const size_t need = 8 + 8 * (size_t)nCoeffs + 8 + sizeof(hpsdf_node) * (size_t)nNodes + sizeof(hpsdf_config);
-    if (nNodes == 0 || nNodes > (size_t)0xFFFFFFF0u || need != size) return fail(HPSDF_ERR_BAD_BLOCK, "node count does not match block size");
-    if (nCoeffs > 0xFFFFFFFFull) return fail(HPSDF_ERR_UNSUPPORTED, "more than 2^32 coefficients");
-    std::vector<hpsdf_node> nodes(nNodes);
-    std::memcpy(nodes.data(), p + 16 + 8 * nCoeffs, sizeof(hpsdf_node) * nNodes);
-    hpsdf_config cfg;
-    std::memcpy(&cfg, p + 16 + 8 * nCoeffs + sizeof(hpsdf_node) * nNodes, sizeof cfg);
-
-    // device mirror: validate that the tree is the dyadic octree the descent recomputes
     const Tables& T = tables();
-    std::vector<NodeRec> recs(nNodes, NodeRec{0, 0});
-    if (nodes[0].degree != kInteriorDegree || nodes[0].child_idx == ~0ull)
-        return fail(HPSDF_ERR_UNSUPPORTED, "root must be an interior node (Octree::CreateRoot always splits it)");
-    for (int a = 0; a < 3; ++a)
-        if (nodes[0].aabb_min[a] != -0.5f || nodes[0].aabb_max[a] != 0.5f)
-            return fail(HPSDF_ERR_UNSUPPORTED, "internal root box must be [-0.5,0.5]^3 (Octree.cpp:798)");
-    if (nNodes < 9) return fail(HPSDF_ERR_BAD_BLOCK, "an interior root needs its 8 children");
-    BlockTreeInfo walk;
+    BlockView v;
+    BlockMirror m;
     {
         std::string why;
-        const int vrc = checkBlockTree(nodes.data(), nNodes, nCoeffs, T.coeffCount, false, false, &walk, why);
-        if (vrc) return fail(vrc, why);
+        int rc = readBlock(block, size, v, why);
+        if (!rc) rc = mirrorBlock(v, T, m, why);  // validates that the tree is the dyadic octree the descent recomputes
+        if (rc) return fail(rc, why);
     }
-    std::vector<double> padded;
-    padded.reserve(nCoeffs + 16 * nNodes);
-    const uint64_t leaves = walk.leaves;
-    const int maxDeg = walk.maxDegree, maxDepth = walk.maxDepth, minLeafDepth = walk.minLeafDepth;
-    for (const uint64_t i : walk.order) {
-        const hpsdf_node& n = nodes[i];
-        if (n.degree == kInteriorDegree) {
-            recs[i] = NodeRec{(uint32_t)n.child_idx, kInteriorTag};
-            for (unsigned c = 0; c < 8; ++c) {
-                const hpsdf_node& ch = nodes[n.child_idx + c];
-                for (int d = 0; d < 3; ++d) {
-                    const float mid = (n.aabb_max[d] + n.aabb_min[d]) * 0.5f;
-                    const float emin = (c >> d) & 1u ? mid : n.aabb_min[d], emax = (c >> d) & 1u ? n.aabb_max[d] : mid;
-                    if (ch.aabb_min[d] != emin || ch.aabb_max[d] != emax)
-                        return fail(HPSDF_ERR_UNSUPPORTED, "child boxes are not midpoint octants of their parent");
-                }
-            }
-        } else {
-            // device mirror: every leaf's block starts on a 128-byte line (the wave-cooperative fetch of
-            // query_general_kernel moves whole lines; a degree-2 leaf is one line, a degree-3 leaf two)
-            recs[i] = NodeRec{(uint32_t)padded.size(), (uint32_t)n.degree};
-            padded.insert(padded.end(), coeffs + n.coeffs_start, coeffs + n.coeffs_start + T.coeffCount[n.degree]);
-            padded.resize((padded.size() + 15) & ~(size_t)15, 0.0);
-        }
-    }
-    if (padded.size() > 0xFFFFFFF0ull) return fail(HPSDF_ERR_UNSUPPORTED, "more than 2^32 coefficients");
     // dense table of the deepest complete level (<= 5): table[path] = node reached by that octant path
-    const int topDepth = std::max(1, std::min(5, minLeafDepth));
+    const int topDepth = std::max(1, std::min(5, m.walk.minLeafDepth));
     std::vector<TopEntry> top((size_t)1 << (3 * topDepth));
     std::vector<NodeRec> topRec(top.size());
     for (size_t code = 0; code < top.size(); ++code) {  // code = x + side * (y + side * z), cell coordinates at topDepth
@@ -893,34 +835,34 @@ int hpsdf_tree_upload(hpsdf_ctx* ctx, const void* block, size_t size, hpsdf_tree
         const size_t kx = code & mask, ky = (code >> topDepth) & mask, kz = code >> (2 * topDepth);
         uint64_t cur = 0;
         for (int l = topDepth - 1; l >= 0; --l)  // bit l of a coordinate picks the upper half at that level (Octree.cpp:1101)
-            cur = nodes[cur].child_idx + ((kx >> l) & 1u) + 2 * ((ky >> l) & 1u) + 4 * ((kz >> l) & 1u);
+            cur = v.nodes[cur].child_idx + ((kx >> l) & 1u) + 2 * ((ky >> l) & 1u) + 4 * ((kz >> l) & 1u);
         TopEntry& te = top[code];
         std::memset(&te, 0, sizeof te);
-        te.a = recs[cur].a;
-        te.b = recs[cur].b;
-        topRec[code] = recs[cur];
+        te.a = m.recs[cur].a;
+        te.b = m.recs[cur].b;
+        topRec[code] = m.recs[cur];
         if (te.b <= 2u)  // small leaf: coefficients ride in the same line
-            std::memcpy(te.c, coeffs + nodes[cur].coeffs_start, sizeof(double) * T.coeffCount[te.b]);
+            std::memcpy(te.c, v.coeffs + v.nodes[cur].coeffs_start, sizeof(double) * T.coeffCount[te.b]);
     }
     HPSDF_HIP(hipSetDevice(ctx->device));
     hpsdf_tree* t = new hpsdf_tree();
     t->device = ctx->device;
-    t->nNodes = nNodes;
-    t->nCoeffs = nCoeffs;
-    t->nLeaves = leaves;
-    t->maxDegree = maxDeg;
-    t->maxDepth = maxDepth;
-    t->allInline = maxDeg <= 2 && maxDepth <= topDepth;
-    t->config = cfg;
-    hipError_t e = hipMalloc((void**)&t->dNodes, nNodes * sizeof(NodeRec));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->dCoeffs, std::max<size_t>(2, padded.size()) * sizeof(double));
+    t->nNodes = v.nNodes;
+    t->nCoeffs = v.nCoeffs;
+    t->nLeaves = m.walk.leaves;
+    t->maxDegree = m.walk.maxDegree;
+    t->maxDepth = m.walk.maxDepth;
+    t->allInline = m.walk.maxDegree <= 2 && m.walk.maxDepth <= topDepth;
+    t->config = v.cfg;
+    hipError_t e = hipMalloc((void**)&t->dNodes, v.nNodes * sizeof(NodeRec));
+    if (e == hipSuccess) e = hipMalloc((void**)&t->dCoeffs, std::max<size_t>(2, m.padded.size()) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&t->dTop, top.size() * sizeof(TopEntry));
     if (e == hipSuccess) e = hipMalloc((void**)&t->dTopRec, topRec.size() * sizeof(NodeRec));
     if (e == hipSuccess) e = hipMemcpy(t->dTopRec, topRec.data(), topRec.size() * sizeof(NodeRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->dNodes, recs.data(), nNodes * sizeof(NodeRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->dNodes, m.recs.data(), v.nNodes * sizeof(NodeRec), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(t->dTop, top.data(), top.size() * sizeof(TopEntry), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !padded.empty())
-        e = hipMemcpy(t->dCoeffs, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !m.padded.empty())
+        e = hipMemcpy(t->dCoeffs, m.padded.data(), m.padded.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         hpsdf_tree_destroy(t);
         return hipFail(e, "tree upload");
@@ -930,13 +872,10 @@ int hpsdf_tree_upload(hpsdf_ctx* ctx, const void* block, size_t size, hpsdf_tree
     t->dev.topRec = t->dTopRec;
     t->dev.coeffs = t->dCoeffs;
     t->dev.topDepth = topDepth;
-    t->dev.maxDegree = maxDeg;
+    t->dev.maxDegree = m.walk.maxDegree;
     for (int j = 0; j < 3; ++j) t->dev.nlTop[j] = T.normalisedLengths[j][topDepth];
-    for (int a = 0; a < 3; ++a) {
-        t->dev.rootCentre[a] = (double)((cfg.root_min[a] + cfg.root_max[a]) / 2.0f);  // Octree.cpp:419
-        t->dev.rootInvSizes[a] = (double)(1.0f / (cfg.root_max[a] - cfg.root_min[a]));  // Octree.cpp:420
-    }
-    t->paddedCount = padded.size();
+    for (int a = 0; a < 3; ++a) t->dev.rootCentre[a] = m.rootCentre[a], t->dev.rootInvSizes[a] = m.rootInvSizes[a];
+    t->paddedCount = m.padded.size();
     *out = t;
     return HPSDF_OK;
     HPSDF_CATCH

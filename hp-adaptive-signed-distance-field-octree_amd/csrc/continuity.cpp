@@ -35,7 +35,7 @@
 #include <thread>
 #include <vector>
 
-#include "block_check.hpp"
+#include "block.hpp"
 #include "continuity.hpp"
 #include "launch.hpp"
 #include "runtime.hpp"
@@ -434,34 +434,9 @@ struct Csr {
     std::vector<double> val;
 };
 
-struct ParsedBlock {
-    uint64_t nCoeffs = 0, nNodes = 0;
-    double* coeffs = nullptr;
-    std::vector<hpsdf_node> nodes;
-    hpsdf_config cfg{};
-};
-
-int parseBlock(void* block, size_t size, ParsedBlock& out, std::string& err) {
-    if (!block || size < 16 + sizeof(hpsdf_config)) {
-        err = "block too small";
-        return HPSDF_ERR_BAD_BLOCK;
-    }
-    uint8_t* p = (uint8_t*)block;
-    std::memcpy(&out.nCoeffs, p, 8);
-    if (out.nCoeffs > (size - 16 - sizeof(hpsdf_config)) / 8) {
-        err = "coefficient count exceeds block";
-        return HPSDF_ERR_BAD_BLOCK;
-    }
-    out.coeffs = (double*)(p + 8);
-    std::memcpy(&out.nNodes, p + 8 + 8 * out.nCoeffs, 8);
-    const size_t need = 8 + 8 * (size_t)out.nCoeffs + 8 + sizeof(hpsdf_node) * (size_t)out.nNodes + sizeof(hpsdf_config);
-    if (out.nNodes == 0 || need != size) {
-        err = "node count does not match block size";
-        return HPSDF_ERR_BAD_BLOCK;
-    }
-    out.nodes.resize(out.nNodes);
-    std::memcpy(out.nodes.data(), p + 16 + 8 * out.nCoeffs, sizeof(hpsdf_node) * out.nNodes);
-    std::memcpy(&out.cfg, p + 16 + 8 * out.nCoeffs + sizeof(hpsdf_node) * out.nNodes, sizeof out.cfg);
+// the block as the assembly and the solve see it: accepted whatever its boxes say, a leaf root included
+int parseBlock(const void* block, size_t size, BlockView& out, std::string& err) {
+    if (const int rc = readBlock(block, size, out, err)) return rc;
     // untrusted bytes: walk from the root (block_check.hpp) -- children in range without wrap-around, no node reached
     // twice (nodeProc recurses along child indices), depths consistent, leaf ranges inside the store and pairwise
     // disjoint (the assembly writes one row block per leaf, in parallel)
@@ -488,7 +463,7 @@ struct Fragment {
 };
 
 // frags: scratch the caller may keep between calls (capacity is reused)
-void assemble(const ParsedBlock& b, Pool& pool, Csr& M, hpsdf_continuity_stats& st, std::vector<Fragment>& frags) {
+void assemble(const BlockView& b, Pool& pool, Csr& M, hpsdf_continuity_stats& st, std::vector<Fragment>& frags) {
     const Tables& T = tables();
     const View view{b.nodes.data(), b.nNodes};
     std::vector<Pair> pairs;
@@ -586,8 +561,8 @@ unsigned poolSize(uint64_t requested) {
 
 int continuityMatrix(const void* block, size_t size, uint64_t threads, uint64_t** rowPtr, uint64_t** col, double** val,
                      hpsdf_continuity_stats* stats, std::string& err) {
-    ParsedBlock b;
-    int rc = parseBlock(const_cast<void*>(block), size, b, err);
+    BlockView b;
+    int rc = parseBlock(block, size, b, err);
     if (rc) return rc;
     Pool pool(poolSize(threads));
     Csr M;
@@ -613,8 +588,8 @@ int continuityMatrix(const void* block, size_t size, uint64_t threads, uint64_t*
 
 int continuityMatrixDevice(hpsdf_ctx* ctx, const void* block, size_t size, uint64_t** rowPtr, uint64_t** col, double** val,
                            hpsdf_continuity_stats* stats, std::string& err) {
-    ParsedBlock b;
-    int rc = parseBlock(const_cast<void*>(block), size, b, err);
+    BlockView b;
+    int rc = parseBlock(block, size, b, err);
     if (rc) return rc;
     hpsdf_continuity_stats st;
     std::memset(&st, 0, sizeof st);
@@ -815,9 +790,10 @@ static int solveOnDevice(hpsdf_ctx* ctx, Keep& keep, const ContinuityDeviceMatri
 int continuityPostProcess(void* block, size_t size, double tol, int maxIter, uint64_t threads,
                           hpsdf_continuity_stats* stats, std::string& err, hpsdf_ctx* ctx) {
     const double tEntry = nowMs();
-    ParsedBlock b;
+    BlockView b;
     int rc = parseBlock(block, size, b, err);
     if (rc) return rc;
+    double* const store = (double*)((uint8_t*)block + kBlockCoeffsAt);  // the block's own coefficients: the solve's result goes there
     hpsdf_continuity_stats st;
     std::memset(&st, 0, sizeof st);
     if (!(b.cfg.continuity_strength > 0.0)) {
@@ -864,7 +840,7 @@ int continuityPostProcess(void* block, size_t size, double tol, int maxIter, uin
         xd.resize(b.nCoeffs);
         rc = solveOnDevice(ctx, keep, onDevice ? &keep.dm : nullptr, b.coeffs, b.cfg.continuity_strength, tol, maxIter, xd.data(), st, err);
         if (rc) return rc;
-        std::memcpy(b.coeffs, xd.data(), sizeof(double) * b.nCoeffs);  // :1756
+        std::memcpy(store, xd.data(), sizeof(double) * b.nCoeffs);  // :1756
         st.assemble_ms = t1 - t0;
         st.solve_ms = nowMs() - t1;
         if (std::getenv("HPSDF_TRACE"))
@@ -962,7 +938,7 @@ int continuityPostProcess(void* block, size_t size, double tol, int maxIter, uin
     st.jump_after = V.dot(x.data(), tmp.data());
     st.iterations = (uint64_t)it;
     st.residual = rhsNorm2 > 0.0 ? std::sqrt(resNorm2 / rhsNorm2) : 0.0;
-    std::memcpy(b.coeffs, x.data(), sizeof(double) * n);  // :1756
+    std::memcpy(store, x.data(), sizeof(double) * n);  // :1756
     st.assemble_ms = t1 - t0;
     st.solve_ms = nowMs() - t1;
     if (std::getenv("HPSDF_TRACE"))

@@ -50,6 +50,7 @@
 #include <memory>
 #include <vector>
 
+#include "block.hpp"
 #include "builder.hpp"
 #include "frontier.hpp"
 #include "launch.hpp"
@@ -2712,12 +2713,12 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
             // a build that stops here has its packed store in pinned memory already (the fit wrote it there too), and everything else
             // of its block is known in advance: write that part while the device works
             const uint64_t nc0 = T.arenaRows, nn0 = T.nNodes;
-            early = (uint8_t*)ctx->allocBlock(8 + 8 * (size_t)nc0 + 8 + sizeof(hpsdf_node) * (size_t)nn0 + sizeof(hpsdf_config));
+            early = (uint8_t*)ctx->allocBlock(blockBytes(nc0, nn0));
             if (early) {
                 std::memcpy(early, &nc0, 8);
-                std::memcpy(early + 8 + 8 * (size_t)nc0, &nn0, 8);
-                std::memcpy(early + 16 + 8 * (size_t)nc0, ws->hostNodesAfterRound0.data(), sizeof(hpsdf_node) * (size_t)nn0);
-                std::memcpy(early + 16 + 8 * (size_t)nc0 + sizeof(hpsdf_node) * (size_t)nn0, &cfg, sizeof cfg);
+                std::memcpy(early + blockNodeCountAt(nc0), &nn0, 8);
+                std::memcpy(early + blockNodesAt(nc0), ws->hostNodesAfterRound0.data(), sizeof(hpsdf_node) * (size_t)nn0);
+                std::memcpy(early + blockConfigAt(nc0, nn0), &cfg, sizeof cfg);
                 // ... and the rows themselves as soon as the closing launch says that the fit before it has finished -- long before it
                 // can say whether the build stops here (the running total is 4096 dependent additions away): 320 KB out of memory the
                 // GPU has just written take a core ~20 us, which now pass while the device works.  In pieces, with an eye on the round
@@ -2730,7 +2731,7 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
                     std::atomic_thread_fence(std::memory_order_acquire);
                     const size_t total = 8 * (size_t)nc0, piece = 32768;
                     size_t at = 0;
-                    for (; at < total && (*roundWord == 0 || *(const volatile uint32_t*)&hh->done); at += piece) std::memcpy(early + 8 + at, ws->pinned + at, std::min(piece, total - at));
+                    for (; at < total && (*roundWord == 0 || *(const volatile uint32_t*)&hh->done); at += piece) std::memcpy(early + kBlockCoeffsAt + at, ws->pinned + at, std::min(piece, total - at));
                     earlyCopied = at >= total;
                 }
             }
@@ -2754,12 +2755,12 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
             std::fprintf(stderr, "\n");
         }
         if (rounds == 1 && world == 1 && hh->done && early && hh->nCoeffs == T.arenaRows && hh->nNodes == T.nNodes) {
-            if (!earlyCopied) std::memcpy(early + 8, ws->pinned, 8 * (size_t)T.arenaRows);
+            if (!earlyCopied) std::memcpy(early + kBlockCoeffsAt, ws->pinned, 8 * (size_t)T.arenaRows);
             hipLaunchKernelGGL(fr_init_kernel, dim3((T.nNodes + 255) / 256), dim3(256), 0, s, initDev(), T0);  // for the next build
             ws->clean = hipGetLastError() == hipSuccess, ws->cleanRank = rank, ws->cleanWorld = world;
             ws->lastWentOn = false;
             *block = early;
-            *size = 8 + 8 * (size_t)T.arenaRows + 8 + sizeof(hpsdf_node) * (size_t)T.nNodes + sizeof(hpsdf_config);
+            *size = blockBytes(T.arenaRows, T.nNodes);
             early = nullptr;
             if (stats) {
                 std::memset(stats, 0, sizeof *stats);
@@ -2843,7 +2844,7 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
         }
         FR_LAUNCH(fr_store_kernel, dim3(((uint32_t)nn + kStoreNodes - 1u) / kStoreNodes), dim3(256), s, d);
     }
-    const size_t bytes = 8 + 8 * (size_t)nc + 8 + sizeof(hpsdf_node) * (size_t)nn + sizeof(hpsdf_config);
+    const size_t bytes = blockBytes(nc, nn);
     uint8_t* p = (uint8_t*)ctx->allocBlock(bytes);
     if (!p) {
         (void)hipStreamSynchronize(s);
@@ -2851,8 +2852,8 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
     }
     const double tc = now();
     std::memcpy(p, &nc, 8);
-    std::memcpy(p + 8 + 8 * (size_t)nc, &nn, 8);
-    std::memcpy(p + 16 + 8 * (size_t)nc + sizeof(hpsdf_node) * (size_t)nn, &cfg, sizeof cfg);
+    std::memcpy(p + blockNodeCountAt(nc), &nn, 8);
+    std::memcpy(p + blockConfigAt(nc, nn), &cfg, sizeof cfg);
     for (int part = 0; part < 2; ++part) {  // 0: the node array, 1: the coefficients
         const volatile uint32_t* flag = &hh->stored[part];
         const double limit = now() + 2.0e3;
@@ -2866,9 +2867,9 @@ int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field*
         }
         std::atomic_thread_fence(std::memory_order_acquire);
         if (part == 0)
-            std::memcpy(p + 16 + 8 * (size_t)nc, ws->pinned + 8 * (size_t)nc, sizeof(hpsdf_node) * (size_t)nn);
+            std::memcpy(p + blockNodesAt(nc), ws->pinned + 8 * (size_t)nc, sizeof(hpsdf_node) * (size_t)nn);
         else
-            std::memcpy(p + 8, ws->pinned, 8 * (size_t)nc);
+            std::memcpy(p + kBlockCoeffsAt, ws->pinned, 8 * (size_t)nc);
     }
     const double tcopy = now() - tc;
     *block = p;

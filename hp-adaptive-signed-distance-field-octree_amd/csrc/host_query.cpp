@@ -14,9 +14,10 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <utility>
 #include <vector>
 
-#include "block_check.hpp"
+#include "block.hpp"
 #include "leaf_gradient.hpp"
 #include "runtime.hpp"
 #include "tables.hpp"
@@ -231,51 +232,18 @@ int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIte
 
 namespace {
 
-// A serialised block as a host-only tree handle: validated like hpsdf_tree_upload validates it and laid out like the device mirror --
-// 8-byte records, every leaf's coefficients on lines of their own -- so the descent and the evaluation are the code above.
+// A serialised block as a host-only tree handle: validated and laid out like the device mirror (block.hpp), so the descent and the
+// evaluation are the code above.
 int treeFromBlock(const void* block, size_t size, hpsdf_tree& t) {
-    if (!block || size < 16 + sizeof(hpsdf_config)) return fail(HPSDF_ERR_BAD_BLOCK, "block too small");
-    const uint8_t* p = (const uint8_t*)block;
-    uint64_t nCoeffs, nNodes;
-    std::memcpy(&nCoeffs, p, 8);
-    if (nCoeffs > (size - 16 - sizeof(hpsdf_config)) / 8) return fail(HPSDF_ERR_BAD_BLOCK, "coefficient count exceeds block");
-    std::memcpy(&nNodes, p + 8 + 8 * nCoeffs, 8);
-    if (nNodes == 0 || nNodes > (size_t)0xFFFFFFF0u || (size - 16 - sizeof(hpsdf_config) - 8 * (size_t)nCoeffs) / sizeof(hpsdf_node) < nNodes ||
-        8 + 8 * (size_t)nCoeffs + 8 + sizeof(hpsdf_node) * (size_t)nNodes + sizeof(hpsdf_config) != size)
-        return fail(HPSDF_ERR_BAD_BLOCK, "node count does not match block size");
-    if (nCoeffs > 0xFFFFFFFFull) return fail(HPSDF_ERR_UNSUPPORTED, "more than 2^32 coefficients");
-    std::vector<double> coeffs(nCoeffs);
-    if (nCoeffs) std::memcpy(coeffs.data(), p + 8, 8 * nCoeffs);
-    std::vector<hpsdf_node> nodes(nNodes);
-    std::memcpy(nodes.data(), p + 16 + 8 * nCoeffs, sizeof(hpsdf_node) * nNodes);
-    hpsdf_config cfg;
-    std::memcpy(&cfg, p + 16 + 8 * nCoeffs + sizeof(hpsdf_node) * nNodes, sizeof cfg);
-    const Tables& T = tables();
-    if (nodes[0].degree != kInteriorDegree || nNodes < 9)
-        return fail(HPSDF_ERR_UNSUPPORTED, "root must be an interior node (Octree::CreateRoot always splits it)");
-    BlockTreeInfo walk;
-    {
-        std::string why;
-        const int vrc = checkBlockTree(nodes.data(), nNodes, nCoeffs, T.coeffCount, false, false, &walk, why);
-        if (vrc) return fail(vrc, why);
-    }
-    t.hRecs.assign(nNodes, NodeRec{0, 0});
-    t.hPadded.reserve(nCoeffs + 16 * nNodes);
-    for (const uint64_t i : walk.order) {
-        const hpsdf_node& nd = nodes[i];
-        if (nd.degree == kInteriorDegree) {
-            t.hRecs[i] = NodeRec{(uint32_t)nd.child_idx, kInteriorTag};
-        } else {
-            t.hRecs[i] = NodeRec{(uint32_t)t.hPadded.size(), (uint32_t)nd.degree};
-            t.hPadded.insert(t.hPadded.end(), coeffs.begin() + nd.coeffs_start, coeffs.begin() + nd.coeffs_start + T.coeffCount[nd.degree]);
-            t.hPadded.resize((t.hPadded.size() + 15) & ~(size_t)15, 0.0);
-        }
-    }
-    if (t.hPadded.size() > 0xFFFFFFF0ull) return fail(HPSDF_ERR_UNSUPPORTED, "more than 2^32 coefficients");
-    for (int a = 0; a < 3; ++a) {
-        t.dev.rootCentre[a] = (double)((cfg.root_min[a] + cfg.root_max[a]) / 2.0f);    // Octree.cpp:419
-        t.dev.rootInvSizes[a] = (double)(1.0f / (cfg.root_max[a] - cfg.root_min[a]));  // Octree.cpp:420
-    }
+    BlockView v;
+    BlockMirror m;
+    std::string why;
+    int rc = readBlock(block, size, v, why);
+    if (!rc) rc = mirrorBlock(v, tables(), m, why);
+    if (rc) return fail(rc, why);
+    t.hRecs = std::move(m.recs);
+    t.hPadded = std::move(m.padded);
+    for (int a = 0; a < 3; ++a) t.dev.rootCentre[a] = m.rootCentre[a], t.dev.rootInvSizes[a] = m.rootInvSizes[a];
     return HPSDF_OK;
 }
 
@@ -288,20 +256,16 @@ int treeFromBlock(const void* block, size_t size, hpsdf_tree& t) {
 extern "C" int hpsdf_query_true_gradient_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out,
                                                double* grad) {
     using namespace hpsdf;
-    try {
-        if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_true_gradient: unknown flag bits");
-        if (n && (!xyz || !grad)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-        hpsdf_tree t;
-        if (const int rc = treeFromBlock(block, size, t)) return rc;
-        const int left = reductionLeftAssoc(nullptr);
-        for (size_t i = 0; i < n; ++i)
-            hostQueryPointTrueGradient(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad + 3 * i);
-        return HPSDF_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& ex) {
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
-    }
+    HPSDF_TRY
+    if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_true_gradient: unknown flag bits");
+    if (n && (!xyz || !grad)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    hpsdf_tree t;
+    if (const int rc = treeFromBlock(block, size, t)) return rc;
+    const int left = reductionLeftAssoc(nullptr);
+    for (size_t i = 0; i < n; ++i)
+        hostQueryPointTrueGradient(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad + 3 * i);
+    return HPSDF_OK;
+    HPSDF_CATCH
 }
 
 // ProjectToSurface from a serialised block, on the calling thread (no device; the process-wide reduction order)
@@ -309,20 +273,16 @@ extern "C" int hpsdf_project_block(const void* block, size_t size, const double*
                                    uint32_t flags, double* out_xyz, double* out_val, double* out_grad, uint8_t* out_iters,
                                    uint8_t* out_status) {
     using namespace hpsdf;
-    try {
-        if (const int rc = projectArgumentError(flags, iso, tol, max_iter)) return rc;
-        if (n && (!xyz || !out_xyz)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-        hpsdf_tree t;
-        if (const int rc = treeFromBlock(block, size, t)) return rc;
-        const int left = reductionLeftAssoc(nullptr);
-        for (size_t i = 0; i < n; ++i)
-            hostProjectPoint(t, xyz + 3 * i, iso, tol, max_iter, (flags & HPSDF_PROJECT_UNIT) != 0u, left, out_xyz + 3 * i,
-                             out_val ? out_val + i : nullptr, out_grad ? out_grad + 3 * i : nullptr, out_iters ? out_iters + i : nullptr,
-                             out_status ? out_status + i : nullptr);
-        return HPSDF_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& ex) {
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
-    }
+    HPSDF_TRY
+    if (const int rc = projectArgumentError(flags, iso, tol, max_iter)) return rc;
+    if (n && (!xyz || !out_xyz)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    hpsdf_tree t;
+    if (const int rc = treeFromBlock(block, size, t)) return rc;
+    const int left = reductionLeftAssoc(nullptr);
+    for (size_t i = 0; i < n; ++i)
+        hostProjectPoint(t, xyz + 3 * i, iso, tol, max_iter, (flags & HPSDF_PROJECT_UNIT) != 0u, left, out_xyz + 3 * i,
+                         out_val ? out_val + i : nullptr, out_grad ? out_grad + 3 * i : nullptr, out_iters ? out_iters + i : nullptr,
+                         out_status ? out_status + i : nullptr);
+    return HPSDF_OK;
+    HPSDF_CATCH
 }

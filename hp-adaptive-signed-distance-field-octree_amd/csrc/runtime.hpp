@@ -5,8 +5,10 @@
 
 #include <cstdint>
 #include <atomic>
+#include <exception>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -196,6 +198,17 @@ int hipFail(hipError_t e, const char* what);
         hipError_t e_ = (call);                                   \
         if (e_ != hipSuccess) return ::hpsdf::hipFail(e_, #call); \
     } while (0)
+
+// the body of an extern "C" entry point: no exception crosses the C ABI
+#define HPSDF_TRY try {
+#define HPSDF_CATCH                                                                    \
+    }                                                                                  \
+    catch (const std::bad_alloc&) {                                                    \
+        return ::hpsdf::fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");       \
+    }                                                                                  \
+    catch (const std::exception& ex) {                                                 \
+        return ::hpsdf::fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what()); \
+    }
 
 // Query / QueryWithGradient of one point on the calling thread (host_query.cpp): the kernels' values bit for bit
 constexpr size_t kHostQueryPoints = 32;     // Query calls of up to this many points never reach the device (capi.cpp: hostQueryLimit)

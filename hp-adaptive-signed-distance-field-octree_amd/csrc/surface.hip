@@ -264,137 +264,133 @@ int hpsdf_surface_last_timings(double* ms) {
 
 int hpsdf_extract_surface(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
                           double** verts, uint64_t* nVerts, uint64_t** tris, uint64_t* nTris, double* values) {
-    try {
-        if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
-        if (!t || !lo || !hi || !n || !verts || !nVerts || !tris || !nTris) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-        *verts = nullptr, *tris = nullptr, *nVerts = 0, *nTris = 0;
-        if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-        if (!std::isfinite(iso)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_extract_surface: iso must be finite");
-        static const char* kAxis[3] = {"x", "y", "z"};
-        SurfaceLattice g{};
-        uint64_t nPts = 1, nCubes = 1;
-        for (int a = 0; a < 3; ++a) {
-            const std::string ax = std::string("hpsdf_extract_surface: axis ") + kAxis[a] + ": ";
-            if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo and hi must be finite");
-            if (!(lo[a] < hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo must be below hi");
-            if (n[a] < 1) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "n must be at least 1");
-            nPts *= (uint64_t)n[a] + 1u;
-            if (nPts > (1ull << 30)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_extract_surface: more than 2^30 lattice points");
-            nCubes *= n[a];
-            g.lo[a] = lo[a];
-            g.h[a] = (hi[a] - lo[a]) / (double)n[a];
-            g.n[a] = n[a];
-            g.np[a] = n[a] + 1u;
-            // the containment test is monotone along an axis: the two extreme lattice points decide for all of them
-            const double last = g.lo[a] + (double)n[a] * g.h[a];
-            if (!inRoot(t->dev, a, g.lo[a]) || !inRoot(t->dev, a, last))
-                return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "the box leaves the tree's root (Query would return DBL_MAX there)");
-        }
-        g.nPts = (uint32_t)nPts;
-        SurfArgs A{};
-        A.g = g;
-        A.iso = iso;
-        A.nEdges = 3 * nPts;
-        A.nWords = (A.nEdges + 63) / 64;
-        A.nCubes = nCubes;
-        A.nTiles = (nCubes + 63) / 64;
-
-        HPSDF_HIP(hipSetDevice(ctx->device));
-        hipStream_t s = ctx->stream;
-        // scratch: values | words | word counts | word prefixes | tile counts | tile prefixes | scan storage
-        size_t tmpW = 0, tmpT = 0;
-        HPSDF_HIP(rocprim::exclusive_scan(nullptr, tmpW, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(A.nWords + 1),
-                                          rocprim::plus<uint64_t>(), s));
-        HPSDF_HIP(rocprim::exclusive_scan(nullptr, tmpT, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(A.nTiles + 1),
-                                          rocprim::plus<uint64_t>(), s));
-        const size_t oVals = 0, oWords = alignUp(oVals + nPts * 8), oWc = alignUp(oWords + A.nWords * 8),
-                     oWp = alignUp(oWc + (A.nWords + 1) * 4), oTc = alignUp(oWp + (A.nWords + 1) * 8), oTp = alignUp(oTc + (A.nTiles + 1) * 4),
-                     oTmp = alignUp(oTp + (A.nTiles + 1) * 8), total = oTmp + std::max(tmpW, tmpT) + 256;
-        DevScratch scratch;
-        {
-            const hipError_t e = hipMalloc(&scratch.p, total);
-            if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-                (void)hipGetLastError();
-                scratch.p = nullptr;
-                return oom("scratch");
-            }
-            HPSDF_HIP(e);
-        }
-        char* base = (char*)scratch.p;
-        double* dV = (double*)(base + oVals);
-        uint64_t* dWords = (uint64_t*)(base + oWords);
-        uint32_t* dWc = (uint32_t*)(base + oWc);
-        uint64_t* dWp = (uint64_t*)(base + oWp);
-        uint32_t* dTc = (uint32_t*)(base + oTc);
-        uint64_t* dTp = (uint64_t*)(base + oTp);
-        void* dTmp = base + oTmp;
-
-        for (double& x : tLastMs) x = 0.0;
-        Events ev;
-        TreeDev td = t->dev;
-        td.leftAssoc = reductionLeftAssoc(ctx);
-        ev.mark(0, s);
-        HPSDF_HIP(launchQueryLattice(s, td, ctx->dTables, g, dV));
-        ev.mark(1, s);
-        HPSDF_HIP(hipMemsetAsync(dWc + A.nWords, 0, 4, s));
-        HPSDF_HIP(hipMemsetAsync(dTc + A.nTiles, 0, 4, s));
-        hipLaunchKernelGGL(surf_edge_words_kernel, dim3(surfGrid(A.nWords * 64)), dim3(kSurfBlock), 0, s, dV, A, dWords, dWc);
-        HPSDF_HIP(hipGetLastError());
-        hipLaunchKernelGGL(surf_tri_count_kernel, dim3(surfGrid(A.nTiles * 64)), dim3(kSurfBlock), 0, s, dV, A, dTc);
-        HPSDF_HIP(hipGetLastError());
-        ev.mark(2, s);
-        HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpW, dWc, dWp, (uint64_t)0, (size_t)(A.nWords + 1), rocprim::plus<uint64_t>(), s));
-        HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpT, dTc, dTp, (uint64_t)0, (size_t)(A.nTiles + 1), rocprim::plus<uint64_t>(), s));
-        ev.mark(3, s);
-        uint64_t counts[2] = {0, 0};
-        HPSDF_HIP(hipMemcpyAsync(&counts[0], dWp + A.nWords, 8, hipMemcpyDeviceToHost, s));
-        HPSDF_HIP(hipMemcpyAsync(&counts[1], dTp + A.nTiles, 8, hipMemcpyDeviceToHost, s));
-        HPSDF_HIP(hipStreamSynchronize(s));
-        const uint64_t V = counts[0], T = counts[1];
-
-        HostOut hv, ht;
-        DevScratch outs;
-        if (T > 0) {
-            hv.p = std::malloc(V * 3 * sizeof(double));
-            ht.p = std::malloc(T * 3 * sizeof(uint64_t));
-            if (!hv.p || !ht.p) return fail(HPSDF_ERR_OUT_OF_MEMORY, "hpsdf_extract_surface: host allocation failed");
-            const size_t oT = alignUp(V * 3 * sizeof(double));
-            const hipError_t e = hipMalloc(&outs.p, oT + T * 3 * sizeof(uint64_t));
-            if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-                (void)hipGetLastError();
-                outs.p = nullptr;
-                return oom("outputs");
-            }
-            HPSDF_HIP(e);
-            double* dVerts = (double*)outs.p;
-            uint64_t* dTris = (uint64_t*)((char*)outs.p + oT);
-            ev.mark(4, s);
-            hipLaunchKernelGGL(surf_vertex_kernel, dim3(surfGrid(A.nWords * 64)), dim3(kSurfBlock), 0, s, dV, A, dWords, dWp, dVerts);
-            HPSDF_HIP(hipGetLastError());
-            hipLaunchKernelGGL(surf_tri_kernel, dim3(surfGrid(A.nTiles * 64)), dim3(kSurfBlock), 0, s, dV, A, dWords, dWp, dTp, dTris);
-            HPSDF_HIP(hipGetLastError());
-            ev.mark(5, s);
-            HPSDF_HIP(hipMemcpyAsync(hv.p, dVerts, V * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-            HPSDF_HIP(hipMemcpyAsync(ht.p, dTris, T * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        }
-        if (values) HPSDF_HIP(hipMemcpyAsync(values, dV, nPts * sizeof(double), hipMemcpyDeviceToHost, s));
-        ev.mark(6, s);
-        HPSDF_HIP(hipStreamSynchronize(s));
-        tLastMs[0] = ev.ms(0, 1), tLastMs[1] = ev.ms(1, 2), tLastMs[2] = ev.ms(2, 3);
-        if (T > 0) tLastMs[3] = ev.ms(4, 5);
-        tLastMs[4] = ev.ms(T > 0 ? 5 : 3, 6);
-        tLastMs[5] = ev.ms(0, 6);
-        if (T > 0) {
-            *verts = (double*)hv.p, *tris = (uint64_t*)ht.p;
-            hv.p = nullptr, ht.p = nullptr;
-            *nVerts = V, *nTris = T;
-        }
-        return HPSDF_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& ex) {
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (!t || !lo || !hi || !n || !verts || !nVerts || !tris || !nTris) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    *verts = nullptr, *tris = nullptr, *nVerts = 0, *nTris = 0;
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    if (!std::isfinite(iso)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_extract_surface: iso must be finite");
+    static const char* kAxis[3] = {"x", "y", "z"};
+    SurfaceLattice g{};
+    uint64_t nPts = 1, nCubes = 1;
+    for (int a = 0; a < 3; ++a) {
+        const std::string ax = std::string("hpsdf_extract_surface: axis ") + kAxis[a] + ": ";
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo and hi must be finite");
+        if (!(lo[a] < hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo must be below hi");
+        if (n[a] < 1) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "n must be at least 1");
+        nPts *= (uint64_t)n[a] + 1u;
+        if (nPts > (1ull << 30)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_extract_surface: more than 2^30 lattice points");
+        nCubes *= n[a];
+        g.lo[a] = lo[a];
+        g.h[a] = (hi[a] - lo[a]) / (double)n[a];
+        g.n[a] = n[a];
+        g.np[a] = n[a] + 1u;
+        // the containment test is monotone along an axis: the two extreme lattice points decide for all of them
+        const double last = g.lo[a] + (double)n[a] * g.h[a];
+        if (!inRoot(t->dev, a, g.lo[a]) || !inRoot(t->dev, a, last))
+            return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "the box leaves the tree's root (Query would return DBL_MAX there)");
     }
+    g.nPts = (uint32_t)nPts;
+    SurfArgs A{};
+    A.g = g;
+    A.iso = iso;
+    A.nEdges = 3 * nPts;
+    A.nWords = (A.nEdges + 63) / 64;
+    A.nCubes = nCubes;
+    A.nTiles = (nCubes + 63) / 64;
+
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // scratch: values | words | word counts | word prefixes | tile counts | tile prefixes | scan storage
+    size_t tmpW = 0, tmpT = 0;
+    HPSDF_HIP(rocprim::exclusive_scan(nullptr, tmpW, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(A.nWords + 1),
+                                      rocprim::plus<uint64_t>(), s));
+    HPSDF_HIP(rocprim::exclusive_scan(nullptr, tmpT, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(A.nTiles + 1),
+                                      rocprim::plus<uint64_t>(), s));
+    const size_t oVals = 0, oWords = alignUp(oVals + nPts * 8), oWc = alignUp(oWords + A.nWords * 8),
+                 oWp = alignUp(oWc + (A.nWords + 1) * 4), oTc = alignUp(oWp + (A.nWords + 1) * 8), oTp = alignUp(oTc + (A.nTiles + 1) * 4),
+                 oTmp = alignUp(oTp + (A.nTiles + 1) * 8), total = oTmp + std::max(tmpW, tmpT) + 256;
+    DevScratch scratch;
+    {
+        const hipError_t e = hipMalloc(&scratch.p, total);
+        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+            (void)hipGetLastError();
+            scratch.p = nullptr;
+            return oom("scratch");
+        }
+        HPSDF_HIP(e);
+    }
+    char* base = (char*)scratch.p;
+    double* dV = (double*)(base + oVals);
+    uint64_t* dWords = (uint64_t*)(base + oWords);
+    uint32_t* dWc = (uint32_t*)(base + oWc);
+    uint64_t* dWp = (uint64_t*)(base + oWp);
+    uint32_t* dTc = (uint32_t*)(base + oTc);
+    uint64_t* dTp = (uint64_t*)(base + oTp);
+    void* dTmp = base + oTmp;
+
+    for (double& x : tLastMs) x = 0.0;
+    Events ev;
+    TreeDev td = t->dev;
+    td.leftAssoc = reductionLeftAssoc(ctx);
+    ev.mark(0, s);
+    HPSDF_HIP(launchQueryLattice(s, td, ctx->dTables, g, dV));
+    ev.mark(1, s);
+    HPSDF_HIP(hipMemsetAsync(dWc + A.nWords, 0, 4, s));
+    HPSDF_HIP(hipMemsetAsync(dTc + A.nTiles, 0, 4, s));
+    hipLaunchKernelGGL(surf_edge_words_kernel, dim3(surfGrid(A.nWords * 64)), dim3(kSurfBlock), 0, s, dV, A, dWords, dWc);
+    HPSDF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(surf_tri_count_kernel, dim3(surfGrid(A.nTiles * 64)), dim3(kSurfBlock), 0, s, dV, A, dTc);
+    HPSDF_HIP(hipGetLastError());
+    ev.mark(2, s);
+    HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpW, dWc, dWp, (uint64_t)0, (size_t)(A.nWords + 1), rocprim::plus<uint64_t>(), s));
+    HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpT, dTc, dTp, (uint64_t)0, (size_t)(A.nTiles + 1), rocprim::plus<uint64_t>(), s));
+    ev.mark(3, s);
+    uint64_t counts[2] = {0, 0};
+    HPSDF_HIP(hipMemcpyAsync(&counts[0], dWp + A.nWords, 8, hipMemcpyDeviceToHost, s));
+    HPSDF_HIP(hipMemcpyAsync(&counts[1], dTp + A.nTiles, 8, hipMemcpyDeviceToHost, s));
+    HPSDF_HIP(hipStreamSynchronize(s));
+    const uint64_t V = counts[0], T = counts[1];
+
+    HostOut hv, ht;
+    DevScratch outs;
+    if (T > 0) {
+        hv.p = std::malloc(V * 3 * sizeof(double));
+        ht.p = std::malloc(T * 3 * sizeof(uint64_t));
+        if (!hv.p || !ht.p) return fail(HPSDF_ERR_OUT_OF_MEMORY, "hpsdf_extract_surface: host allocation failed");
+        const size_t oT = alignUp(V * 3 * sizeof(double));
+        const hipError_t e = hipMalloc(&outs.p, oT + T * 3 * sizeof(uint64_t));
+        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+            (void)hipGetLastError();
+            outs.p = nullptr;
+            return oom("outputs");
+        }
+        HPSDF_HIP(e);
+        double* dVerts = (double*)outs.p;
+        uint64_t* dTris = (uint64_t*)((char*)outs.p + oT);
+        ev.mark(4, s);
+        hipLaunchKernelGGL(surf_vertex_kernel, dim3(surfGrid(A.nWords * 64)), dim3(kSurfBlock), 0, s, dV, A, dWords, dWp, dVerts);
+        HPSDF_HIP(hipGetLastError());
+        hipLaunchKernelGGL(surf_tri_kernel, dim3(surfGrid(A.nTiles * 64)), dim3(kSurfBlock), 0, s, dV, A, dWords, dWp, dTp, dTris);
+        HPSDF_HIP(hipGetLastError());
+        ev.mark(5, s);
+        HPSDF_HIP(hipMemcpyAsync(hv.p, dVerts, V * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HPSDF_HIP(hipMemcpyAsync(ht.p, dTris, T * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    }
+    if (values) HPSDF_HIP(hipMemcpyAsync(values, dV, nPts * sizeof(double), hipMemcpyDeviceToHost, s));
+    ev.mark(6, s);
+    HPSDF_HIP(hipStreamSynchronize(s));
+    tLastMs[0] = ev.ms(0, 1), tLastMs[1] = ev.ms(1, 2), tLastMs[2] = ev.ms(2, 3);
+    if (T > 0) tLastMs[3] = ev.ms(4, 5);
+    tLastMs[4] = ev.ms(T > 0 ? 5 : 3, 6);
+    tLastMs[5] = ev.ms(0, 6);
+    if (T > 0) {
+        *verts = (double*)hv.p, *tris = (uint64_t*)ht.p;
+        hv.p = nullptr, ht.p = nullptr;
+        *nVerts = V, *nTris = T;
+    }
+    return HPSDF_OK;
+    HPSDF_CATCH
 }
 
 }  // extern "C"

@@ -31,7 +31,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "block_check.hpp"
+#include "block.hpp"
 #include "device_types.hpp"
 #include "leaf_eval.hpp"
 #include "runtime.hpp"
@@ -784,68 +784,37 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
     return HPSDF_OK;
 }
 
-// a serialised block -> the arrays the walk reads, as hpsdf_tree_upload lays them out (capi.cpp) -- with the constants
+// a serialised block -> the arrays the walk reads: the query mirror (block.hpp) and the constants
 struct HostTree {
-    std::vector<NodeRec> recs;
-    std::vector<double> padded, consts;
+    BlockMirror m;
+    std::vector<double> consts;
     ClsTree view{};
 };
 
 int parseBlock(const void* block, size_t size, HostTree* out) {
-    if (!block || size < 16 + sizeof(hpsdf_config)) return fail(HPSDF_ERR_BAD_BLOCK, "block too small");
-    const uint8_t* p = (const uint8_t*)block;
-    uint64_t nCoeffs, nNodes;
-    std::memcpy(&nCoeffs, p, 8);
-    if (nCoeffs > (size - 16 - sizeof(hpsdf_config)) / 8) return fail(HPSDF_ERR_BAD_BLOCK, "coefficient count exceeds block");
-    std::memcpy(&nNodes, p + 8 + 8 * nCoeffs, 8);
-    if (nNodes == 0 || nNodes > (size_t)0xFFFFFFF0u || (size - 16 - sizeof(hpsdf_config) - 8 * (size_t)nCoeffs) / sizeof(hpsdf_node) < nNodes ||
-        8 + 8 * (size_t)nCoeffs + 8 + sizeof(hpsdf_node) * (size_t)nNodes + sizeof(hpsdf_config) != size)
-        return fail(HPSDF_ERR_BAD_BLOCK, "node count does not match block size");
-    if (nCoeffs > 0xFFFFFFFFull) return fail(HPSDF_ERR_UNSUPPORTED, "more than 2^32 coefficients");
-    std::vector<double> coeffs(nCoeffs);
-    if (nCoeffs) std::memcpy(coeffs.data(), p + 8, 8 * nCoeffs);
-    std::vector<hpsdf_node> nodes(nNodes);
-    std::memcpy(nodes.data(), p + 16 + 8 * nCoeffs, sizeof(hpsdf_node) * nNodes);
-    hpsdf_config cfg;
-    std::memcpy(&cfg, p + 16 + 8 * nCoeffs + sizeof(hpsdf_node) * nNodes, sizeof cfg);
+    BlockView v;
+    BlockMirror& m = out->m;
     const Tables& T = tables();
-    if (nodes[0].degree != kInteriorDegree || nNodes < 9) return fail(HPSDF_ERR_UNSUPPORTED, "root must be an interior node (Octree::CreateRoot always splits it)");
-    BlockTreeInfo walk;
     {
         std::string why;
-        const int vrc = checkBlockTree(nodes.data(), nNodes, nCoeffs, T.coeffCount, false, false, &walk, why);
-        if (vrc) return fail(vrc, why);
+        int rc = readBlock(block, size, v, why);
+        if (!rc) rc = mirrorBlock(v, T, m, why);
+        if (rc) return fail(rc, why);
     }
     uint8_t bidx[kMaxCoeffs][4];
     for (int i = 0; i < kMaxCoeffs; ++i)
         for (int k = 0; k < 3; ++k) bidx[i][k] = (uint8_t)T.basisIndex[i][k];
-    out->recs.assign(nNodes, NodeRec{0, 0});
-    out->consts.assign(4 * (size_t)nNodes, 0.0);
-    out->padded.clear();
-    out->padded.reserve(nCoeffs + 16 * nNodes);
-    for (const uint64_t i : walk.order) {
-        const hpsdf_node& nd = nodes[i];
-        if (nd.degree == kInteriorDegree) {
-            out->recs[i] = NodeRec{(uint32_t)nd.child_idx, kInteriorTag};
-        } else {
-            out->recs[i] = NodeRec{(uint32_t)out->padded.size(), (uint32_t)nd.degree};
-            out->padded.insert(out->padded.end(), coeffs.begin() + nd.coeffs_start, coeffs.begin() + nd.coeffs_start + T.coeffCount[nd.degree]);
-            out->padded.resize((out->padded.size() + 15) & ~(size_t)15, 0.0);
-        }
-    }
-    for (const uint64_t i : walk.order) {
-        const NodeRec rec = out->recs[i];
-        if (rec.b <= 12u && walk.depthOf[i] <= HPSDF_TREE_MAX_DEPTH)
-            leafBound(out->padded.data() + rec.a, (uint32_t)T.coeffCount[rec.b], walk.depthOf[i], &T.normalisedLengths[0][0], bidx,
+    out->consts.assign(4 * (size_t)v.nNodes, 0.0);
+    for (const uint64_t i : m.walk.order) {
+        const NodeRec rec = m.recs[i];
+        if (rec.b <= 12u && m.walk.depthOf[i] <= HPSDF_TREE_MAX_DEPTH)
+            leafBound(m.padded.data() + rec.a, (uint32_t)T.coeffCount[rec.b], m.walk.depthOf[i], &T.normalisedLengths[0][0], bidx,
                       out->consts.data() + 4 * i);
     }
-    out->view.nodes = out->recs.data();
-    out->view.coeffs = out->padded.data();
+    out->view.nodes = m.recs.data();
+    out->view.coeffs = m.padded.data();
     out->view.consts = out->consts.data();
-    for (int a = 0; a < 3; ++a) {
-        out->view.rootCentre[a] = (double)((cfg.root_min[a] + cfg.root_max[a]) / 2.0f);  // Octree.cpp:419
-        out->view.rootInvSizes[a] = (double)(1.0f / (cfg.root_max[a] - cfg.root_min[a]));  // Octree.cpp:420
-    }
+    for (int a = 0; a < 3; ++a) out->view.rootCentre[a] = m.rootCentre[a], out->view.rootInvSizes[a] = m.rootInvSizes[a];
     return HPSDF_OK;
 }
 
@@ -859,69 +828,57 @@ extern "C" {
 
 int hpsdf_extract_surface_sparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
                                  double** verts, uint64_t* nVerts, uint64_t** tris, uint64_t* nTris, hpsdf_surface_sparse_stats* stats) {
-    try {
-        if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
-        if (!t || !lo || !hi || !n || !verts || !nVerts || !tris || !nTris) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-        *verts = nullptr, *tris = nullptr, *nVerts = 0, *nTris = 0;
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-        return extractSparse(ctx, t, lo, hi, n, iso, verts, nVerts, tris, nTris, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& ex) {
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
-    }
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (!t || !lo || !hi || !n || !verts || !nVerts || !tris || !nTris) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    *verts = nullptr, *tris = nullptr, *nVerts = 0, *nTris = 0;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    return extractSparse(ctx, t, lo, hi, n, iso, verts, nVerts, tris, nTris, stats);
+    HPSDF_CATCH
 }
 
 int hpsdf_surface_classify_host(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
                                 uint64_t first_block, uint64_t count, uint8_t* out) {
-    try {
-        static const char* kWhat = "hpsdf_surface_classify_host";
-        if (!lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-        HostTree ht;
-        if (const int rc = parseBlock(block, size, &ht)) return rc;
-        SparseLattice g{};
-        if (const int rc = makeLattice(kWhat, ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
-        if (first_block > g.nBlocks || count > g.nBlocks - first_block)
-            return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
-        const HostEval eval{&tables()};
-        for (uint64_t i = 0; i < count; ++i) {
-            uint32_t visited;
-            out[i] = classifyBlock(ht.view, g, iso, first_block + i, eval, visited);
-        }
-        return HPSDF_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& ex) {
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
+    HPSDF_TRY
+    static const char* kWhat = "hpsdf_surface_classify_host";
+    if (!lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    HostTree ht;
+    if (const int rc = parseBlock(block, size, &ht)) return rc;
+    SparseLattice g{};
+    if (const int rc = makeLattice(kWhat, ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
+    if (first_block > g.nBlocks || count > g.nBlocks - first_block)
+        return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
+    const HostEval eval{&tables()};
+    for (uint64_t i = 0; i < count; ++i) {
+        uint32_t visited;
+        out[i] = classifyBlock(ht.view, g, iso, first_block + i, eval, visited);
     }
+    return HPSDF_OK;
+    HPSDF_CATCH
 }
 
 int hpsdf_surface_classify_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3], double iso,
                                   uint64_t first_block, uint64_t count, uint8_t* out) {
-    try {
-        static const char* kWhat = "hpsdf_surface_classify_device";
-        if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
-        if (!t || !lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-        if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-        SparseLattice g{};
-        if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
-        if (first_block > g.nBlocks || count > g.nBlocks - first_block)
-            return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
-        if (count == 0) return HPSDF_OK;
-        HPSDF_HIP(hipSetDevice(ctx->device));
-        DevPool pool;
-        uint8_t* dClass = nullptr;
-        SPARSE_ALLOC(pool, dClass, (size_t)count, "block classes");
-        if (const int rc = classifyOnDevice(kWhat, ctx, t, pool, g, iso, first_block, count, dClass, nullptr)) return rc;
-        HPSDF_HIP(hipMemcpyAsync(out, dClass, (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
-        HPSDF_HIP(hipStreamSynchronize(ctx->stream));
-        return HPSDF_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& ex) {
-        return fail(HPSDF_ERR_STATE, std::string("exception: ") + ex.what());
-    }
+    HPSDF_TRY
+    static const char* kWhat = "hpsdf_surface_classify_device";
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (!t || !lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    SparseLattice g{};
+    if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
+    if (first_block > g.nBlocks || count > g.nBlocks - first_block)
+        return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
+    if (count == 0) return HPSDF_OK;
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    DevPool pool;
+    uint8_t* dClass = nullptr;
+    SPARSE_ALLOC(pool, dClass, (size_t)count, "block classes");
+    if (const int rc = classifyOnDevice(kWhat, ctx, t, pool, g, iso, first_block, count, dClass, nullptr)) return rc;
+    HPSDF_HIP(hipMemcpyAsync(out, dClass, (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+    HPSDF_HIP(hipStreamSynchronize(ctx->stream));
+    return HPSDF_OK;
+    HPSDF_CATCH
 }
 
 }  // extern "C"

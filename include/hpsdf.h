@@ -326,7 +326,9 @@ HPSDF_API int hpsdf_query_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, con
  * out may be NULL (gradients only).  Unknown flag bits, a NULL grad with n > 0 or a NULL tree: HPSDF_ERR_INVALID_ARGUMENT.  n == 0 is
  * HPSDF_OK.  _device is asynchronous on the context stream; _host answers calls of up to 32 points on the calling thread
  * (csrc/host_query.cpp) and sends larger ones through the device; _block needs no device at all: it evaluates from a serialised
- * block on the calling thread, under the process-wide reduction order (a malformed block: HPSDF_ERR_BAD_BLOCK).  All three give the
+ * block on the calling thread, under the process-wide reduction order.  It accepts exactly the blocks hpsdf_tree_upload accepts, with
+ * upload's status for the others: HPSDF_ERR_BAD_BLOCK for a malformed block (a root without its 8 children included),
+ * HPSDF_ERR_UNSUPPORTED for a root box other than [-0.5,0.5]^3 or child boxes that are not midpoint octants.  All three give the
  * same bits. */
 #define HPSDF_GRADIENT_UNIT 1u
 HPSDF_API int hpsdf_query_true_gradient_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_xyz, size_t n, uint32_t flags,
@@ -363,7 +365,8 @@ HPSDF_API int hpsdf_query_true_gradient_block(const void* block, size_t size, co
  * Unknown flag bits, a NULL out_xyz (or input) with n > 0, a NULL tree, tol negative or NaN, a non-finite iso, max_iter > 255:
  * HPSDF_ERR_INVALID_ARGUMENT, and no output is written.  n == 0 is HPSDF_OK.  _device is asynchronous on the context stream; _host
  * answers calls of up to 32 points on the calling thread and sends larger ones through the device; _block needs no device: it works
- * from a serialised block on the calling thread under the process-wide reduction order (a malformed block: HPSDF_ERR_BAD_BLOCK). */
+ * from a serialised block on the calling thread under the process-wide reduction order, and accepts and refuses blocks as
+ * hpsdf_tree_upload does (malformed: HPSDF_ERR_BAD_BLOCK; boxes the descent would not recompute: HPSDF_ERR_UNSUPPORTED). */
 #define HPSDF_PROJECT_UNIT 1u
 enum { HPSDF_PROJECT_CONVERGED = 0, HPSDF_PROJECT_ITER_LIMIT = 1, HPSDF_PROJECT_LEFT_ROOT = 2, HPSDF_PROJECT_FLAT = 3 };
 HPSDF_API int hpsdf_project_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_xyz, size_t n, double iso, double tol,

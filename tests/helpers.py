@@ -116,6 +116,56 @@ def synthetic_block(rng, degrees, depth=1, root_min=(-0.5,) * 3, root_max=(0.5,)
     return blk
 
 
+def block_reader_table():
+    """Blocks for the checks every reader of a MemoryBlock shares (csrc/block.hpp): [(name, bytes, status of the query paths)] with status
+    "ok", "bad_block" or "unsupported".  The base is synthetic_block(rng, [2] * 8, depth=2) -- 17 nodes -- with continuity.strength set,
+    so that the continuity post-process takes it too; the first row is that block unedited."""
+    blk = bytearray(synthetic_block(np.random.default_rng(1), [2] * 8, depth=2))
+    blk[-80 + 24:-80 + 32] = np.array([1.0]).tobytes()
+    blk = bytes(blk)
+    nc = int(np.frombuffer(blk[:8], np.uint64)[0])
+    nn = int(np.frombuffer(blk[8 + 8 * nc:16 + 8 * nc], np.uint64)[0])
+    assert nn == 17
+    base = 16 + 8 * nc
+
+    def put(at, value, dtype=np.uint64):
+        b = bytearray(blk)
+        raw = np.array([value], dtype).tobytes()
+        b[at:at + len(raw)] = raw
+        return bytes(b)
+
+    def edit(node, off, value, dtype=np.uint64):
+        return put(base + 56 * node + off, value, dtype)
+
+    tiny = bytearray(16 + 56)
+    tiny[8:16] = np.array([1], np.uint64).tobytes()
+    tiny[16:24] = np.array([1 << 40], np.uint64).tobytes()
+    tiny[16 + 8:16 + 32] = np.array([-0.5] * 3 + [0.5] * 3, np.float32).tobytes()
+    tiny[16 + 40] = 13
+    bad = {
+        "child index 1<<40": edit(0, 0, 1 << 40),
+        "children run past the end": edit(0, 0, nn - 3),
+        "child is the root": edit(1, 0, 0),
+        "child is its own parent block": edit(1, 0, 1),
+        "coefficient start wraps": edit(2, 32, 0xFFFFFFFFFFFFFFFC),
+        "coefficient start past the store": edit(2, 32, nc - 1),
+        "leaf degree 200": edit(2, 40, 200, np.uint8),
+        "leaf depth lies": edit(2, 48, 3, np.uint8),
+        "1-node interior root": bytes(tiny) + blk[-80:],
+        "one byte short": blk[:-1],
+        "100 bytes": blk[:100],
+        "8 bytes": blk[:8],
+        "empty": b"",
+        "node count + 2^61": put(8 + 8 * nc, nn + (1 << 61)),   # 56 * 2^61 = 0 mod 2^64: a size computed in 64 bits still "matches"
+        "node count + 1": put(8 + 8 * nc, nn + 1),
+    }
+    boxes = {
+        "root box max.x = 0.4": edit(0, 20, 0.4, np.float32),
+        "child 1 min.x = -0.4": edit(1, 8, -0.4, np.float32),
+    }
+    return [("unedited", blk, "ok")] + [(k, v, "bad_block") for k, v in bad.items()] + [(k, v, "unsupported") for k, v in boxes.items()]
+
+
 def icosphere(level=1, radius=0.35, centre=(0.0, 0.0, 0.0)):
     """Closed, consistently CCW (outward) triangle mesh: 20 * 4^level triangles."""
     t = (1.0 + 5.0 ** 0.5) / 2.0

@@ -6,7 +6,7 @@
 #include <string>
 #include <functional>
 #include <vector>
-#include "block_check.hpp"
+#include "block.hpp"
 #include "builder.hpp"
 #include "continuity.hpp"
 #include "launch.hpp"
@@ -155,16 +155,28 @@ int main(int argc, char** argv) {
     { std::vector<char> b(blk.begin(), blk.end() - 8); hpsdf_continuity_stats st; if (!hpsdf::continuityPostProcess(b.data(), b.size(), 0, 0, 1, &st, err)) return 4; }
     // malformed blocks (untrusted bytes): each must come back as an error, under ASAN/UBSAN, not crash
     {
-        auto mutate = [&](const char* what, const std::function<void(std::vector<char>&, uint64_t, uint64_t, hpsdf_node*)>& edit) -> int {
+        // what the query paths make of the same bytes (block.hpp: hpsdf_tree_upload and the *_block entry points)
+        auto mirrorRc = [&](const void* bytes, size_t size) -> int {
+            hpsdf::BlockView v;
+            hpsdf::BlockMirror m;
+            std::string why;
+            int rc = hpsdf::readBlock(bytes, size, v, why);
+            if (!rc) rc = hpsdf::mirrorBlock(v, hpsdf::tables(), m, why);
+            if (rc && why.empty()) return -1;  // every refusal says why
+            return rc;
+        };
+        auto mutate = [&](const char* what, const std::function<void(std::vector<char>&, uint64_t, uint64_t, hpsdf_node*)>& edit,
+                          int mirrorWant = HPSDF_ERR_BAD_BLOCK) -> int {
             std::vector<char> b = blk;
             uint64_t nc, nn;
             memcpy(&nc, b.data(), 8);
-            memcpy(&nn, b.data() + 8 + 8 * nc, 8);
-            edit(b, nc, nn, (hpsdf_node*)(b.data() + 16 + 8 * nc));
+            memcpy(&nn, b.data() + hpsdf::blockNodeCountAt(nc), 8);
+            edit(b, nc, nn, (hpsdf_node*)(b.data() + hpsdf::blockNodesAt(nc)));
+            const int mrc = mirrorRc(b.data(), b.size());  // (before the post-process: a block it accepts it also rewrites)
             hpsdf_continuity_stats st;
             const int rc = hpsdf::continuityPostProcess(b.data(), b.size(), 0, 0, 2, &st, err);
             printf("malformed block (%s): rc %d (%s)\n", what, rc, err.c_str());
-            return rc == HPSDF_ERR_BAD_BLOCK ? 0 : 1;
+            return (rc == HPSDF_ERR_BAD_BLOCK ? 0 : 1) + (mrc == mirrorWant ? 0 : 1);
         };
         int bad = 0;
         bad += mutate("child index 1<<40", [](std::vector<char>&, uint64_t, uint64_t, hpsdf_node* n) { n[0].child_idx = 1ull << 40; });
@@ -177,20 +189,41 @@ int main(int argc, char** argv) {
             for (uint64_t i = 0; i < nn; ++i) if (n[i].child_idx == ~0ull) { n[i].coeffs_start = nc - 1; break; } });
         bad += mutate("two leaves share coefficients", [](std::vector<char>&, uint64_t, uint64_t nn, hpsdf_node* n) {
             uint64_t first = ~0ull;
-            for (uint64_t i = 0; i < nn; ++i) if (n[i].child_idx == ~0ull) { if (first == ~0ull) first = i; else { n[i].coeffs_start = n[first].coeffs_start; break; } } });
+            for (uint64_t i = 0; i < nn; ++i) if (n[i].child_idx == ~0ull) { if (first == ~0ull) first = i; else { n[i].coeffs_start = n[first].coeffs_start; break; } } },
+                      HPSDF_OK);  // (only the assembly needs disjoint leaves)
         bad += mutate("leaf degree 200", [](std::vector<char>&, uint64_t, uint64_t nn, hpsdf_node* n) {
             for (uint64_t i = 0; i < nn; ++i) if (n[i].child_idx == ~0ull) { n[i].degree = 200; break; } });
         bad += mutate("leaf depth lies", [](std::vector<char>&, uint64_t, uint64_t nn, hpsdf_node* n) {
             for (uint64_t i = 0; i < nn; ++i) if (n[i].child_idx == ~0ull) { n[i].depth = 1; break; } });
+        // the node count raised by 2^61 (56 * 2^61 wraps to 0: the size still "matches") and by 1; truncated blocks; boxes the descent
+        // does not recompute -- refused by the query mirror, not read by the post-process
+        bad += mutate("node count + 2^61", [](std::vector<char>& b, uint64_t nc, uint64_t nn, hpsdf_node*) {
+            nn += 1ull << 61; memcpy(b.data() + hpsdf::blockNodeCountAt(nc), &nn, 8); });
+        bad += mutate("node count + 1", [](std::vector<char>& b, uint64_t nc, uint64_t nn, hpsdf_node*) {
+            nn += 1; memcpy(b.data() + hpsdf::blockNodeCountAt(nc), &nn, 8); });
+        for (size_t keep : {blk.size() - 1, (size_t)100, (size_t)8, (size_t)0}) {
+            std::vector<char> b(blk.begin(), blk.begin() + keep);
+            hpsdf_continuity_stats st;
+            if (mirrorRc(b.data(), b.size()) != HPSDF_ERR_BAD_BLOCK || hpsdf::continuityPostProcess(b.data(), b.size(), 0, 0, 1, &st, err) != HPSDF_ERR_BAD_BLOCK) ++bad;
+        }
+        for (int which = 0; which < 2; ++which) {
+            std::vector<char> b = blk;
+            uint64_t nc;
+            memcpy(&nc, b.data(), 8);
+            hpsdf_node* n = (hpsdf_node*)(b.data() + hpsdf::blockNodesAt(nc));
+            if (which == 0) n[0].aabb_max[0] = 0.4f; else n[1].aabb_min[0] = -0.4f;
+            if (mirrorRc(b.data(), b.size()) != HPSDF_ERR_UNSUPPORTED) ++bad;
+        }
+        if (mirrorRc(blk.data(), blk.size()) != HPSDF_OK) ++bad;
         if (bad) return 40;
         {
             // random corruption of the node array (1 to 4 bytes anywhere in it, or a field set to an awkward value): the validator
-            // both deserialisers share must say yes or no without leaving the array -- 6 000 blocks, both strictness levels, under the sanitizers
+            // every deserialiser shares must say yes or no without leaving the array -- 6 000 blocks, both strictness levels, under the sanitizers
             uint64_t nc, nn;
             memcpy(&nc, blk.data(), 8);
-            memcpy(&nn, blk.data() + 8 + 8 * nc, 8);
+            memcpy(&nn, blk.data() + hpsdf::blockNodeCountAt(nc), 8);
             std::vector<hpsdf_node> nodes(nn), work;
-            memcpy(nodes.data(), blk.data() + 16 + 8 * nc, nn * sizeof(hpsdf_node));
+            memcpy(nodes.data(), blk.data() + hpsdf::blockNodesAt(nc), nn * sizeof(hpsdf_node));
             unsigned long long x = 0x9E3779B97F4A7C15ull;
             auto rnd = [&]() { x ^= x << 13, x ^= x >> 7, x ^= x << 17; return x; };
             const uint64_t awkward[] = {0ull, 1ull, 8ull, nn - 1, nn, nn + 1, ~0ull, ~0ull - 7, 1ull << 32, 1ull << 63, nc, nc - 1, nc + 1};
@@ -214,13 +247,15 @@ int main(int argc, char** argv) {
             printf("block fuzz: 6000 corrupted node arrays, %d verdicts 'valid'\n", stillValid);
         }
         // one interior root and nothing else: nNodes < 9
-        std::vector<char> tiny(16 + sizeof(hpsdf_node) + sizeof(hpsdf_config), 0);
+        std::vector<char> tiny(hpsdf::blockBytes(0, 1), 0);
         const uint64_t one = 1;
-        memcpy(tiny.data() + 8, &one, 8);
-        hpsdf_node* root = (hpsdf_node*)(tiny.data() + 16);
+        memcpy(tiny.data() + hpsdf::blockNodeCountAt(0), &one, 8);
+        hpsdf_node* root = (hpsdf_node*)(tiny.data() + hpsdf::blockNodesAt(0));
         root->child_idx = 1ull << 40;
         root->degree = 13;
+        for (int a = 0; a < 3; ++a) root->aabb_min[a] = -0.5f, root->aabb_max[a] = 0.5f;
         hpsdf_continuity_stats st;
+        if (mirrorRc(tiny.data(), tiny.size()) != HPSDF_ERR_BAD_BLOCK) return 41;
         if (hpsdf::continuityPostProcess(tiny.data(), tiny.size(), 0, 0, 1, &st, err) != HPSDF_ERR_BAD_BLOCK) return 41;
         printf("malformed block (1-node interior root): %s\n", err.c_str());
     }
@@ -274,34 +309,17 @@ int main(int argc, char** argv) {
         // the block.  Here, under the sanitizers and without a GPU: a handle filled the way hpsdf_tree_upload fills it, the points of
         // argv[4] (f64 xyz) in, values and gradients out to argv[5] -- tests/test_sanitizers.py compares them with the oracle bit for bit.
         if (const char* e = getenv("HPSDF_REDUCTION_ORDER")) hpsdf::setReductionLeftAssoc(e[0] == 'l');
-        uint64_t nc, nn;
-        memcpy(&nc, blk.data(), 8);
-        memcpy(&nn, blk.data() + 8 + 8 * nc, 8);
         // (the arrays of the device mirror, as hpsdf_tree_upload lays them out and hpsdf_tree::hostCopies() fetches them: 8-byte node
         // records, every leaf's coefficients padded to whole 128-byte lines)
         hpsdf_tree tree;
         {
-            std::vector<hpsdf_node> nodes(nn);
-            memcpy(nodes.data(), blk.data() + 16 + 8 * nc, nn * sizeof(hpsdf_node));
-            const double* coeffs = (const double*)(blk.data() + 8);
-            tree.hRecs.resize(nn);
-            for (uint64_t i = 0; i < nn; ++i) {
-                if (nodes[i].child_idx != ~0ull) {
-                    tree.hRecs[i].a = (uint32_t)nodes[i].child_idx, tree.hRecs[i].b = hpsdf::kInteriorTag;
-                } else {
-                    const uint64_t cnt = hpsdf::tables().coeffCount[nodes[i].degree];
-                    tree.hRecs[i].a = (uint32_t)tree.hPadded.size(), tree.hRecs[i].b = nodes[i].degree;
-                    tree.hPadded.insert(tree.hPadded.end(), coeffs + nodes[i].coeffs_start, coeffs + nodes[i].coeffs_start + cnt);
-                    tree.hPadded.resize((tree.hPadded.size() + 15) & ~(size_t)15, 0.0);
-                }
-            }
+            hpsdf::BlockView v;
+            hpsdf::BlockMirror m;
+            if (hpsdf::readBlock(blk.data(), blk.size(), v, err) || hpsdf::mirrorBlock(v, hpsdf::tables(), m, err)) return 10;
+            tree.hRecs = std::move(m.recs);
+            tree.hPadded = std::move(m.padded);
+            for (int a = 0; a < 3; ++a) tree.dev.rootCentre[a] = m.rootCentre[a], tree.dev.rootInvSizes[a] = m.rootInvSizes[a];
             tree.hostReady = true;
-        }
-        hpsdf_config cfg;
-        memcpy(&cfg, blk.data() + 16 + 8 * nc + nn * sizeof(hpsdf_node), sizeof cfg);
-        for (int a = 0; a < 3; ++a) {
-            tree.dev.rootCentre[a] = (double)((cfg.root_min[a] + cfg.root_max[a]) / 2.0f);
-            tree.dev.rootInvSizes[a] = (double)(1.0f / (cfg.root_max[a] - cfg.root_min[a]));
         }
         FILE* pf = fopen(argv[4], "rb");
         fseek(pf, 0, SEEK_END); long psz = ftell(pf); fseek(pf, 0, SEEK_SET);

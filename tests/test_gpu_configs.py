@@ -631,6 +631,33 @@ def test_upload_rejects_malformed_blocks(H, ctx):
         t.FromMemoryBlock(b"\x00" * 40)  # smaller than two counts + Config
 
 
+def test_upload_and_block_paths_share_one_reader(H, ctx):
+    """csrc/block.hpp: hpsdf_tree_upload and the *_block entry points read and mirror a block with the same code -- the same verdict on
+    every block of the table, and the same gradients from the same mirror: 8 points are answered on the host from the mirror the
+    tree downloads, 40 by the kernel, and both are the block path's bits."""
+    import ctypes as C
+    from helpers import block_reader_table
+    L = H.lib()
+    pts = np.random.default_rng(9).uniform(-0.55, 0.55, (40, 3))
+    out, grad = np.empty(40), np.empty((40, 3))
+    for name, blk, want in block_reader_table():
+        handle = C.c_void_p()
+        up = L.hpsdf_tree_upload(ctx.handle, blk, len(blk), C.byref(handle))
+        if up == H.OK:
+            L.hpsdf_tree_destroy(handle)
+        got = L.hpsdf_query_true_gradient_block(blk, len(blk), pts.ctypes.data_as(C.c_void_p), 40, 0, out.ctypes.data_as(C.c_void_p),
+                                                grad.ctypes.data_as(C.c_void_p))
+        assert up == got, (name, up, got)
+        assert up == {"ok": H.OK, "bad_block": H.ERR_BAD_BLOCK, "unsupported": H.ERR_UNSUPPORTED}[want], name
+    blk = block_reader_table()[0][1]
+    tree = H.DeviceTree(ctx, blk)
+    for n in (8, 40):
+        v, g = tree.query_gradient(pts[:n])
+        bv, bg = H.query_gradient_block(blk, pts[:n])
+        assert np.array_equal(bits(v), bits(bv)) and np.array_equal(bits(g), bits(bg)), n
+    assert (bv == np.finfo(np.float64).max).any() and (bv != np.finfo(np.float64).max).sum() > 20
+
+
 # ------------------------------------------------------------------ the device-side frontier (csrc/frontier.hip)
 @pytest.mark.parametrize("name,target,K", [("union3", 1e-5, 1024), ("union3", 1e-7, 1024), ("union3", 1e-7, 256),
                                            ("sphere", 1e-8, 1024), ("union3", 1e-8, 4096), ("sphere075", 1e-6, 64)])
