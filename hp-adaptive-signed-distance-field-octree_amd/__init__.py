@@ -155,6 +155,12 @@ _SIGNATURES = {
     "hpsdf_query_true_gradient_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "hpsdf_query_true_gradient_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "hpsdf_query_true_gradient_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "hpsdf_query_hessian_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "hpsdf_query_hessian_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "hpsdf_query_hessian_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "hpsdf_project_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_project_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
@@ -612,6 +618,34 @@ class DeviceTree:
         check(lib().hpsdf_query_true_gradient_device(self.ctx.handle, self.handle, C.c_void_p(d_xyz_ptr), n, GRADIENT_UNIT if unit else 0,
                                                      C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(d_grad_ptr)))
 
+    def query_hessian(self, pts, unit=False, curvature=False):
+        """QueryHessian (include/hpsdf.h): Query's values, QueryGradient's gradients and the second derivative of the polynomial they come
+        from -> (values f64 [n], grad f64 [n,3], hess f64 [n,6]: xx, yy, zz, xy, xz, yz), and with curvature curv f64 [n,2]: the level
+        set's (mean, gauss).  unit: the gradient rows normalised.  Outside the root: DBL_MAX, NaN rows."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = len(pts)
+        out, grad, hess = np.empty(n), np.empty((n, 3)), np.empty((n, 6))
+        curv = np.empty((n, 2)) if curvature else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib().hpsdf_query_hessian_host(self.ctx.handle, self.handle, vp(pts), n, GRADIENT_UNIT if unit else 0, vp(out), vp(grad),
+                                             vp(hess), vp(curv)))
+        return (out, grad, hess, curv) if curvature else (out, grad, hess)
+
+    def query_curvature(self, pts):
+        """The level set's (mean, gauss) curvature at the points alone (hpsdf_query_hessian_host with only curv) -> f64 [n,2]."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        curv = np.empty((len(pts), 2))
+        check(lib().hpsdf_query_hessian_host(self.ctx.handle, self.handle, pts.ctypes.data_as(C.c_void_p), len(pts), 0, None, None, None,
+                                             curv.ctypes.data_as(C.c_void_p)))
+        return curv
+
+    def query_hessian_device(self, d_xyz_ptr, n, d_out_ptr=0, d_grad_ptr=0, d_hess_ptr=0, d_curv_ptr=0, unit=False):
+        """Raw device pointers (ints; 0 = NULL for any output, but not for d_hess_ptr and d_curv_ptr both); asynchronous on the context
+        stream."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        check(lib().hpsdf_query_hessian_device(self.ctx.handle, self.handle, vp(d_xyz_ptr), n, GRADIENT_UNIT if unit else 0, vp(d_out_ptr),
+                                               vp(d_grad_ptr), vp(d_hess_ptr), vp(d_curv_ptr)))
+
     def project(self, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
         """ProjectToSurface (include/hpsdf.h): Newton's iteration along the gradient onto {Query = iso}, per point until |f - iso| <= tol
         -> (points f64 [n,3], values f64 [n], grad f64 [n,3], iters u8 [n], status u8 [n]); (values, grad) is query_gradient(points, unit)
@@ -1062,6 +1096,25 @@ class Octree:
         out, grad = self._tree.query_gradient(a, unit)
         return (float(out[0]), grad[0]) if a.ndim == 1 else (out, grad)
 
+    def QueryHessian(self, pts, unit=False, curvature=False):
+        """The field's second derivative (DeviceTree.query_hessian): one point (3,) -> (float, grad (3,), hess (6,): xx, yy, zz, xy, xz,
+        yz), or (n,3) -> (values, grad [n,3], hess [n,6]); curvature appends the level set's (mean, gauss): (2,) or [n,2]."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        a = np.asarray(pts, np.float64)
+        res = self._tree.query_hessian(a, unit, curvature)
+        return (float(res[0][0]),) + tuple(r[0] for r in res[1:]) if a.ndim == 1 else res
+
+    def QueryCurvature(self, points):
+        """(mean, gauss) curvature of the level set through every point: one point (3,) -> two floats, or (n,3) -> two arrays [n].  With
+        the field positive outside, a sphere of radius r gives (1/r, 1/r^2).  Leaves of degree <= 2 give a crude answer (zero or a
+        constant Hessian): use a refined tree."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        a = np.asarray(points, np.float64)
+        curv = self._tree.query_curvature(a)
+        return (float(curv[0, 0]), float(curv[0, 1])) if a.ndim == 1 else (curv[:, 0].copy(), curv[:, 1].copy())
+
     def ProjectToSurface(self, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
         """The points moved onto the level set {Query = iso} along the gradient (DeviceTree.project): one point (3,) -> (point (3,),
         value, grad (3,), iters, status) with scalars, or (n,3) -> the five arrays."""
@@ -1088,16 +1141,22 @@ class Octree:
         write_bmp(fname + ".bmp", rgb)
         return rgb
 
-    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False, normals=False, project=False, tol=1e-9, max_iter=16):
+    def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False, normals=False, project=False, tol=1e-9, max_iter=16,
+                       curvature=False):
         """Triangle mesh of the level set {Query = iso} over the box [view_min, view_max] with n cubes per axis (an int or three)
         -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice.  sparse: the same arrays through
         DeviceTree.extract_surface_sparse (lattices up to 2^40 points).  project: the vertices -- linear interpolants along lattice
         edges -- are moved onto the polynomial's level set (DeviceTree.project_vertices with tol and max_iter: a vertex moves only if
         its projection converged within half a cube of it); tris is unchanged.  normals: (verts, tris, normals f64 [V,3]) with
-        normals = query_gradient(verts, unit=True)[1], the field's unit gradient at every vertex (the projected ones under project)."""
+        normals = query_gradient(verts, unit=True)[1], the field's unit gradient at every vertex (the projected ones under project).
+        curvature: a last array f64 [V,2] is appended, query_curvature(verts): the level set's (mean, gauss) at the final vertices;
+        verts and tris are the same bytes with and without it."""
         if self._tree is None:
             raise HpsdfError(6, "Query on an empty octree")
         n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
+        if curvature:
+            res = self.ExtractSurface(view_min, view_max, n3, iso, sparse, normals, project, tol, max_iter)
+            return res + (self._tree.query_curvature(res[0]),)
         if normals:
             verts, tris = self.ExtractSurface(view_min, view_max, n3, iso, sparse, False, project, tol, max_iter)
             return verts, tris, self._tree.query_gradient(verts, unit=True)[1]
@@ -1178,6 +1237,19 @@ def project_block(block, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
     check(lib().hpsdf_project_block(buf, len(buf), vp(pts), n, float(iso), float(tol), _max_iter(max_iter), PROJECT_UNIT if unit else 0,
                                     vp(out), vp(val), vp(grad), vp(iters), vp(status)))
     return out, val, grad, iters, status
+
+
+def query_hessian_block(block, pts, unit=False, curvature=False):
+    """hpsdf_query_hessian_block: DeviceTree.query_hessian's arrays from a serialised block on the calling thread (no device; the
+    process-wide reduction order) -> (values f64 [n], grad f64 [n,3], hess f64 [n,6]) and, with curvature, curv f64 [n,2]."""
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+    n = len(pts)
+    out, grad, hess = np.empty(n), np.empty((n, 3)), np.empty((n, 6))
+    curv = np.empty((n, 2)) if curvature else None
+    buf = bytes(block)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    check(lib().hpsdf_query_hessian_block(buf, len(buf), vp(pts), n, GRADIENT_UNIT if unit else 0, vp(out), vp(grad), vp(hess), vp(curv)))
+    return (out, grad, hess, curv) if curvature else (out, grad, hess)
 
 
 def query_gradient_block(block, pts, unit=False):

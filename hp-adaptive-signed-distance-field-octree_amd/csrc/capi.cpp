@@ -1042,6 +1042,53 @@ int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const do
     HPSDF_CATCH
 }
 
+// QueryHessian (include/hpsdf.h): value, gradient, second derivative and level-set curvature (query_hessian.hip, host_query.cpp)
+int hpsdf_query_hessian_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz, size_t n, uint32_t flags, double* dOut, double* dGrad,
+                               double* dHess, double* dCurv) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = hessianArgumentError(flags, dXyz, n, dHess, dCurv)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (n == 0) return HPSDF_OK;
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    TreeDev td = t->dev;
+    td.leftAssoc = reductionLeftAssoc(ctx);
+    HPSDF_HIP(launchQueryHessian(ctx->stream, td, ctx->dTables, dXyz, n, flags, dOut, dGrad, dHess, dCurv));
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+int hpsdf_query_hessian_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, uint32_t flags, double* out, double* grad,
+                             double* hess, double* curv) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = hessianArgumentError(flags, xyz, n, hess, curv)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (n == 0) return HPSDF_OK;
+    if (n <= kHostQueryPoints && smallQueriesOnHost()) {
+        if (const int hc = t->hostCopies()) return hc;
+        const int left = reductionLeftAssoc(ctx);
+        for (size_t i = 0; i < n; ++i)
+            hostQueryPointHessian(*t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr,
+                                  grad ? grad + 3 * i : nullptr, hess ? hess + 6 * i : nullptr, curv ? curv + 2 * i : nullptr);
+        return HPSDF_OK;
+    }
+    // the input first, then the outputs asked for
+    HostArray arr[5] = {{xyz, nullptr, n * 3 * sizeof(double)}};
+    int used = 1, iOut = -1, iGrad = -1, iHess = -1, iCurv = -1;
+    if (out) arr[iOut = used++] = HostArray{nullptr, out, n * sizeof(double)};
+    if (grad) arr[iGrad = used++] = HostArray{nullptr, grad, n * 3 * sizeof(double)};
+    if (hess) arr[iHess = used++] = HostArray{nullptr, hess, n * 6 * sizeof(double)};
+    if (curv) arr[iCurv = used++] = HostArray{nullptr, curv, n * 2 * sizeof(double)};
+    return hostCall(ctx, arr, used, [&] {
+        return hpsdf_query_hessian_device(ctx, t, (const double*)arr[0].dev, n, flags, iOut < 0 ? nullptr : (double*)arr[iOut].dev,
+                                          iGrad < 0 ? nullptr : (double*)arr[iGrad].dev, iHess < 0 ? nullptr : (double*)arr[iHess].dev,
+                                          iCurv < 0 ? nullptr : (double*)arr[iCurv].dev);
+    });
+    HPSDF_CATCH
+}
+
 // ProjectToSurface (include/hpsdf.h): Newton's iteration onto {Query = iso} (project.hip, host_query.cpp)
 int hpsdf_project_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz, size_t n, double iso, double tol, uint32_t maxIter,
                          uint32_t flags, double* dOutXyz, double* dOutVal, double* dOutGrad, uint8_t* dOutIters, uint8_t* dOutStatus) {

@@ -19,6 +19,7 @@
 
 #include "block.hpp"
 #include "leaf_gradient.hpp"
+#include "leaf_hessian.hpp"
 #include "runtime.hpp"
 #include "tables.hpp"
 
@@ -200,6 +201,39 @@ void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool uni
     grad[0] = g[0], grad[1] = g[1], grad[2] = g[2];
 }
 
+// QueryHessian (include/hpsdf.h): Query's descent, then value, gradient, second derivative and curvature with the statements the kernels
+// run (leaf_hessian.hpp; query_hessian.hip).  Every output may be null.  Outside the root: DBL_MAX and quiet NaNs.
+void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad, double* hess,
+                           double* curv) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    double f = DBL_MAX, g[3] = {nan, nan, nan}, H[6] = {nan, nan, nan, nan, nan, nan}, k[2] = {nan, nan};
+    Leaf L;
+    if (descend(t, xyz, L)) {
+        const Tables& T = tables();
+        double gu[3], hu[6];
+        f = leafHessian(
+            L.co, L.degree, (int)T.coeffCount[L.degree], L.u, L.depth, &T.normalisedLengths[0][0], &T.recurrence[0][0],
+            [&T](int r, int c) { return (int)T.basisIndex[r][c]; }, gu, hu);
+        finishTrueGradient(gu, L.depth, t.dev.rootInvSizes, false, leftAssoc, g);
+        finishHessian(hu, L.depth, t.dev.rootInvSizes, H);
+        if (curv) levelSetCurvature(g, H, leftAssoc, k);
+        if (unit) unitGradient(g, leftAssoc);
+    }
+    if (out) *out = f;
+    if (grad) grad[0] = g[0], grad[1] = g[1], grad[2] = g[2];
+    if (hess)
+        for (int a = 0; a < 6; ++a) hess[a] = H[a];
+    if (curv) curv[0] = k[0], curv[1] = k[1];
+}
+
+// what hpsdf_query_hessian_* reject before anything runs (0: fine)
+int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const double* hess, const double* curv) {
+    if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_hessian: unknown flag bits");
+    if (n && !xyz) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (!hess && !curv) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_hessian: hess and curv are both null");
+    return HPSDF_OK;
+}
+
 // ProjectToSurface (include/hpsdf.h) for one point: the loop of project.hip's projectPoint on the routine above.  xyz and outXyz may be
 // the same three doubles; every output but outXyz may be null.
 void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc, double* outXyz,
@@ -264,6 +298,22 @@ extern "C" int hpsdf_query_true_gradient_block(const void* block, size_t size, c
     const int left = reductionLeftAssoc(nullptr);
     for (size_t i = 0; i < n; ++i)
         hostQueryPointTrueGradient(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad + 3 * i);
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+// QueryHessian from a serialised block, on the calling thread (no device; the process-wide reduction order)
+extern "C" int hpsdf_query_hessian_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out, double* grad,
+                                         double* hess, double* curv) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (const int rc = hessianArgumentError(flags, xyz, n, hess, curv)) return rc;
+    hpsdf_tree t;
+    if (const int rc = treeFromBlock(block, size, t)) return rc;
+    const int left = reductionLeftAssoc(nullptr);
+    for (size_t i = 0; i < n; ++i)
+        hostQueryPointHessian(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad ? grad + 3 * i : nullptr,
+                              hess ? hess + 6 * i : nullptr, curv ? curv + 2 * i : nullptr);
     return HPSDF_OK;
     HPSDF_CATCH
 }

@@ -36,6 +36,9 @@ hipError_t launchFitWeight(hipStream_t stream, const FitBlock* dBlocks, uint32_t
 // ---- QueryGradient (query_gradient.hip): value (dOut may be null) and the polynomial's own gradient; flags: HPSDF_GRADIENT_UNIT
 hipError_t launchQueryTrueGradient(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
                                    uint32_t flags, double* dOut, double* dGrad, bool allInline);
+// ---- QueryHessian (query_hessian.hip): value, gradient, Hessian (6 a point) and (mean, gauss) curvature; every output may be null
+hipError_t launchQueryHessian(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n, uint32_t flags,
+                              double* dOut, double* dGrad, double* dHess, double* dCurv);
 // ---- ProjectToSurface (project.hip): Newton's iteration onto {Query = iso}; dOutXyz may be dXyz, the other outputs may be null
 struct ProjectArgs {
     double iso, tol;

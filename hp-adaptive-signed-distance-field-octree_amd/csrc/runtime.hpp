@@ -222,6 +222,10 @@ bool hostQueryRay(const hpsdf_tree& t, const double* origin, const double* dir, 
 // QueryGradient of one point on the calling thread (host_query.cpp; the arithmetic is leaf_gradient.hpp's): *out (may be null) and
 // grad[0..2]; outside the root DBL_MAX and three quiet NaNs
 void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad);
+// QueryHessian of one point on the calling thread (host_query.cpp; the arithmetic is leaf_hessian.hpp's): every output may be null
+void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad, double* hess,
+                           double* curv);
+int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const double* hess, const double* curv);
 // ProjectToSurface of one point on the calling thread (host_query.cpp): the kernels' rows bit for bit; every output but outXyz may be
 // null, outXyz may be xyz.  projectArgumentError: the argument checks the three hpsdf_project_* entries share (sets the message)
 void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc, double* outXyz,

@@ -338,6 +338,47 @@ HPSDF_API int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t
 HPSDF_API int hpsdf_query_true_gradient_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out,
                                               double* grad);
 
+/* ---- QueryHessian: the value, the gradient and the second derivative of the polynomial the value comes from, and the mean and
+ * Gaussian curvature of its level set through the point (no reference counterpart).
+ *
+ * The arithmetic, for host and device alike (no fused multiply-add anywhere; every sum starts from 0.0 and runs in basis order):
+ *   Query's own remap, f32 containment test and descent (a point on a mid-plane takes the upper child).  In the leaf -- degree p, depth
+ *   d, unit coordinates u and the table nl as in QueryGradient -- per axis a:
+ *     L_j, D_j, LN_j, DN_j    exactly QueryGradient's
+ *     E_0 = E_1 = 0,  E_j = E_{j-2} + (double)(2j-1) D_{j-1}  for j >= 2      (= L_j'')
+ *     EN_j = E_j nl[j][d]
+ *   over rows r = (a,b,c):
+ *     f       Query's bits, and gu_0..2 QueryGradient's bits: the same statements in the same order
+ *     hu_xx += c_r ((EN_a LN_b) LN_c),  hu_yy += c_r ((LN_a EN_b) LN_c),  hu_zz += c_r ((LN_a LN_b) EN_c)
+ *     hu_xy += c_r ((DN_a DN_b) LN_c),  hu_xz += c_r ((DN_a LN_b) DN_c),  hu_yz += c_r ((LN_a DN_b) DN_c)
+ *   world Hessian, with s = (double)(2 << d):  H_ab = (((hu_ab s) s) rootInvSizes[a]) rootInvSizes[b]
+ *     hess holds 6 doubles per point in the order xx, yy, zz, xy, xz, yz.
+ *   world gradient g: QueryGradient's, not normalised.  HPSDF_GRADIENT_UNIT in flags normalises only the gradient row that is written
+ *     out; the curvature always uses the un-normalised g.
+ *   curvature, curv[2] = (mean, gauss), with sum3(a,b,c) = a + (b + c), or (a + b) + c under hpsdf_[ctx_]set_reduction_order(1):
+ *     z = sum3(g0 g0, g1 g1, g2 g2);  if !(z > 0): both entries are quiet NaN
+ *     Hg_a = sum3(H_a0 g0, H_a1 g1, H_a2 g2);  q = sum3(g0 Hg_0, g1 Hg_1, g2 Hg_2);  tr = sum3(H_xx, H_yy, H_zz)
+ *     mean = (z tr - q) / ((2.0 z) sqrt(z))
+ *     A00 = Hyy Hzz - Hyz Hyz,  A11 = Hxx Hzz - Hxz Hxz,  A22 = Hxx Hyy - Hxy Hxy
+ *     A01 = Hxz Hyz - Hxy Hzz,  A02 = Hxy Hyz - Hxz Hyy,  A12 = Hxy Hxz - Hxx Hyz        (A symmetric)
+ *     Ag_a = sum3(A_a0 g0, A_a1 g1, A_a2 g2);  k = sum3(g0 Ag_0, g1 Ag_1, g2 Ag_2);  gauss = k / (z z)
+ *     Sign convention: with the field positive outside, a sphere of radius r has mean = 1/r and gauss = 1/r^2.
+ *   Outside the root, or a NaN coordinate: the value is DBL_MAX and every other output row is quiet NaNs.
+ * Caveat: the field is piecewise polynomial and discontinuous across cell faces, and so are its derivatives.  Leaves of degree <= 1 have
+ * a zero Hessian and leaves of degree 2 a constant one; trees built at the default thresholds hold leaves of degree <= 2 only, so the
+ * curvature they give is crude.  Curvature is meaningful on refined trees (smaller targets, higher degrees).
+ * Each of out, grad, hess and curv may be NULL, but hess and curv must not both be NULL.  Unknown flag bits, a NULL tree, or NULL points
+ * with n > 0: HPSDF_ERR_INVALID_ARGUMENT, and nothing is written.  n == 0 is HPSDF_OK.  _device is asynchronous on the context stream;
+ * _host answers calls of up to 32 points on the calling thread (csrc/host_query.cpp) and sends larger ones through the device; _block
+ * needs no device: it evaluates from a serialised block on the calling thread under the process-wide reduction order, and accepts and
+ * refuses blocks exactly as hpsdf_query_true_gradient_block does.  All three give the same bits. */
+HPSDF_API int hpsdf_query_hessian_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_xyz, size_t n, uint32_t flags, double* d_out,
+                                         double* d_grad, double* d_hess, double* d_curv);
+HPSDF_API int hpsdf_query_hessian_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, size_t n, uint32_t flags, double* out,
+                                       double* grad, double* hess, double* curv);
+HPSDF_API int hpsdf_query_hessian_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out, double* grad,
+                                        double* hess, double* curv);
+
 /* ---- ProjectToSurface: Newton's iteration along the gradient onto the level set {Query = iso} (no reference counterpart).
  * Per point, with iso finite, tol >= 0 (not NaN) and max_iter in 0..255; host, device and block entries run the same statements (no
  * fused multiply-add anywhere) and give the same bits:

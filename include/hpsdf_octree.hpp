@@ -484,6 +484,33 @@ class Octree {
         return normals;
     }
 
+    /// The value, the gradient and the second derivative of the field Query returns, and optionally the mean and Gaussian curvature of
+    /// its level set through the point (no reference counterpart; include/hpsdf.h, "QueryHessian").  hessian_: the six entries xx, yy,
+    /// zz, xy, xz, yz of the symmetric matrix.  unit_: the gradient normalised.  Outside the root: DBL_MAX and NaNs
+    f64 QueryHessian(const Eigen::Vector3d& pt_, Eigen::Vector3d& gradient_, f64 (&hessian_)[6], bool unit_ = false, f64* mean_ = nullptr,
+                     f64* gauss_ = nullptr) const {
+        const double xyz[3] = {pt_(0), pt_(1), pt_(2)};
+        double out = 0.0, g[3] = {0.0, 0.0, 0.0}, k[2] = {0.0, 0.0};
+        QueryHessian(xyz, 1, &out, g, hessian_, (mean_ || gauss_) ? k : nullptr, unit_);
+        gradient_ = Eigen::Vector3d(g[0], g[1], g[2]);
+        if (mean_) *mean_ = k[0];
+        if (gauss_) *gauss_ = k[1];
+        return out;
+    }
+    /// Batched form over host arrays: hess 6 doubles a point (xx, yy, zz, xy, xz, yz), curv 2 (mean, gauss); every output may be null
+    /// but not hess and curv both
+    void QueryHessian(const double* xyz, usize n, double* out, double* grad, double* hess, double* curv = nullptr, bool unit_ = false) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        check(hpsdf_query_hessian_host(ctx_, t, xyz, n, unit_ ? HPSDF_GRADIENT_UNIT : 0u, out, grad, hess, curv));
+    }
+    /// (mean, gauss) curvature of the level set at every vertex of a mesh ExtractSurface returned, 2 doubles a vertex
+    std::vector<double> SurfaceCurvature(const SurfaceMesh& mesh_) const {
+        std::vector<double> curv(mesh_.vertices.size() / 3 * 2);
+        if (!curv.empty()) QueryHessian(mesh_.vertices.data(), mesh_.vertices.size() / 3, nullptr, nullptr, nullptr, curv.data());
+        return curv;
+    }
+
     /// Sphere tracing along ray_ (<= 200 Query steps).  As in the reference (Octree.cpp:705-746), t_ receives
     /// the field value at the stopping point on a hit and is left untouched otherwise   (Octree.h:75)
     bool QueryRay(const Ray& ray_, const f64 tMax_, f64& t_) const {
