@@ -169,6 +169,15 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_surface_project_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.c_double, C.c_double,
                                                  C.c_uint32, C.POINTER(C.c_uint64)]),
+    "hpsdf_cast_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
+                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "hpsdf_cast_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
+                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "hpsdf_cast_rays_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
+                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -679,6 +688,29 @@ class DeviceTree:
                                                    float(tol), _max_iter(max_iter), C.byref(moved)))
         return v, int(moved.value)
 
+    def cast_rays(self, origins, directions, t_max, iso=0.0, tol=1e-9, max_iter=32, max_cells=4096, unit=False):
+        """CastRays (include/hpsdf.h): the first crossing of each ray o + t d (t in [0, t_max], d as given) with {Query = iso}: the
+        ray is walked leaf by leaf and the first sign change refined until |f - iso| <= tol -> (status u8 [n], t f64 [n], points f64
+        [n,3], values f64 [n], grad f64 [n,3], evals u16 [n], cells u16 [n]); (values, grad) is query_gradient(points, unit) bit for
+        bit.  status: CAST_HIT, CAST_MISS, CAST_UNCONVERGED (a sign change that sits on a jump across a cell face, or max_iter too
+        small: the row is the first sample behind it), CAST_CELL_LIMIT, CAST_INVALID; t and the row are NaN for MISS, CELL_LIMIT
+        and INVALID."""
+        o, d, tm, n = _ray_arrays(origins, directions, t_max)
+        bufs = _cast_outputs(n)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().hpsdf_cast_rays_host(self.ctx.handle, self.handle, vp(o), vp(d), vp(tm), n, float(iso), float(tol), _max_iter(max_iter),
+                                         _max_iter(max_cells), CAST_UNIT if unit else 0, *[vp(b) for b in bufs]))
+        return bufs
+
+    def cast_rays_device(self, d_origins_ptr, d_dirs_ptr, d_t_max_ptr, n, d_out_status_ptr, d_out_t_ptr=0, d_out_xyz_ptr=0, d_out_val_ptr=0,
+                         d_out_grad_ptr=0, d_out_evals_ptr=0, d_out_cells_ptr=0, iso=0.0, tol=1e-9, max_iter=32, max_cells=4096, unit=False):
+        """Raw device pointers (ints; 0 = NULL for every output but d_out_status_ptr); asynchronous on the context stream."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        check(lib().hpsdf_cast_rays_device(self.ctx.handle, self.handle, vp(d_origins_ptr), vp(d_dirs_ptr), vp(d_t_max_ptr), n, float(iso),
+                                           float(tol), _max_iter(max_iter), _max_iter(max_cells), CAST_UNIT if unit else 0,
+                                           vp(d_out_status_ptr), vp(d_out_t_ptr), vp(d_out_xyz_ptr), vp(d_out_val_ptr), vp(d_out_grad_ptr),
+                                           vp(d_out_evals_ptr), vp(d_out_cells_ptr)))
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1124,6 +1156,18 @@ class Octree:
         out, val, grad, iters, status = self._tree.project(a, iso, tol, max_iter, unit)
         return (out[0], float(val[0]), grad[0], int(iters[0]), int(status[0])) if a.ndim == 1 else (out, val, grad, iters, status)
 
+    def CastRays(self, origins, directions, t_max, iso=0.0, tol=1e-9, max_iter=32, max_cells=4096, unit=False):
+        """Where each ray first crosses the level set {Query = iso} (DeviceTree.cast_rays): one ray (3,), (3,) -> (status, t, point
+        (3,), value, grad (3,), evals, cells) with scalars, or (n,3) arrays -> the seven arrays.  Unlike QueryRay -- the reference's
+        sphere tracing -- the direction is used as given, t is the ray parameter, and a hit lies within tol of the level set."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        o = np.asarray(origins, np.float64)
+        st, t, pts, val, grad, evals, cells = self._tree.cast_rays(o, directions, t_max, iso, tol, max_iter, max_cells, unit)
+        if o.ndim == 1:
+            return int(st[0]), float(t[0]), pts[0], float(val[0]), grad[0], int(evals[0]), int(cells[0])
+        return st, t, pts, val, grad, evals, cells
+
     def QueryRay(self, origins, directions, t_max):
         """Octree::QueryRay (Octree.h:75) for one ray -> (hit, t) or (n,3) arrays -> (hit[n], t[n])."""
         if self._tree is None:
@@ -1213,6 +1257,10 @@ PROJECT_UNIT = 1  # HPSDF_PROJECT_UNIT
 PROJECT_CONVERGED, PROJECT_ITER_LIMIT, PROJECT_LEFT_ROOT, PROJECT_FLAT = 0, 1, 2, 3  # HPSDF_PROJECT_*: out_status
 
 
+CAST_UNIT = 1  # HPSDF_CAST_UNIT
+CAST_HIT, CAST_MISS, CAST_UNCONVERGED, CAST_CELL_LIMIT, CAST_INVALID = 0, 1, 2, 3, 4  # HPSDF_CAST_*: out_status
+
+
 def _max_iter(max_iter):
     m = int(max_iter)
     if m < 0:
@@ -1237,6 +1285,31 @@ def project_block(block, pts, iso=0.0, tol=1e-9, max_iter=16, unit=False):
     check(lib().hpsdf_project_block(buf, len(buf), vp(pts), n, float(iso), float(tol), _max_iter(max_iter), PROJECT_UNIT if unit else 0,
                                     vp(out), vp(val), vp(grad), vp(iters), vp(status)))
     return out, val, grad, iters, status
+
+
+def _ray_arrays(origins, directions, t_max):
+    o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+    if len(d) != len(o):
+        raise ValueError("origins and directions must have the same number of rows")
+    return o, d, np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float64), (len(o),))), len(o)
+
+
+def _cast_outputs(n):
+    return (np.empty(n, np.uint8), np.empty(n), np.empty((n, 3)), np.empty(n), np.empty((n, 3)), np.empty(n, np.uint16),
+            np.empty(n, np.uint16))
+
+
+def cast_rays_block(block, origins, directions, t_max, iso=0.0, tol=1e-9, max_iter=32, max_cells=4096, unit=False):
+    """hpsdf_cast_rays_block: DeviceTree.cast_rays' arrays from a serialised block on the calling thread (no device; the process-wide
+    reduction order) -> (status u8 [n], t f64 [n], points f64 [n,3], values f64 [n], grad f64 [n,3], evals u16 [n], cells u16 [n])."""
+    o, d, tm, n = _ray_arrays(origins, directions, t_max)
+    bufs = _cast_outputs(n)
+    buf = bytes(block)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().hpsdf_cast_rays_block(buf, len(buf), vp(o), vp(d), vp(tm), n, float(iso), float(tol), _max_iter(max_iter),
+                                      _max_iter(max_cells), CAST_UNIT if unit else 0, *[vp(b) for b in bufs]))
+    return bufs
 
 
 def query_hessian_block(block, pts, unit=False, curvature=False):

@@ -21,6 +21,7 @@
 #include "frontier.hpp"
 #include "block.hpp"
 #include "launch.hpp"
+#include "ray_cast.hpp"
 #include "runtime.hpp"
 
 using namespace hpsdf;
@@ -1134,6 +1135,63 @@ int hpsdf_project_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, s
         return hpsdf_project_device(ctx, t, (const double*)arr[0].dev, n, iso, tol, maxIter, flags, (double*)arr[1].dev,
                                     iVal < 0 ? nullptr : (double*)arr[iVal].dev, iGrad < 0 ? nullptr : (double*)arr[iGrad].dev,
                                     iIters < 0 ? nullptr : (uint8_t*)arr[iIters].dev, iStatus < 0 ? nullptr : (uint8_t*)arr[iStatus].dev);
+    });
+    HPSDF_CATCH
+}
+
+// CastRays (include/hpsdf.h): the first crossing of each ray with {Query = iso} (cast_rays.hip, host_query.cpp)
+int hpsdf_cast_rays_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dOrigins, const double* dDirs, const double* dTMax, size_t n,
+                           double iso, double tol, uint32_t maxIter, uint32_t maxCells, uint32_t flags, uint8_t* dOutStatus, double* dOutT,
+                           double* dOutXyz, double* dOutVal, double* dOutGrad, uint16_t* dOutEvals, uint16_t* dOutCells) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = castArgumentError(flags, iso, tol, maxIter, maxCells, n, dOrigins, dDirs, dTMax, dOutStatus)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (n == 0) return HPSDF_OK;
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    TreeDev td = t->dev;
+    td.leftAssoc = reductionLeftAssoc(ctx);
+    HPSDF_HIP(launchCastRays(ctx->stream, td, ctx->dTables, dOrigins, dDirs, dTMax, n, CastArgs{iso, tol, maxIter, maxCells, flags, 0u},
+                             dOutStatus, dOutT, dOutXyz, dOutVal, dOutGrad, dOutEvals, dOutCells));
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+int hpsdf_cast_rays_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* origins, const double* dirs, const double* tMax, size_t n, double iso,
+                         double tol, uint32_t maxIter, uint32_t maxCells, uint32_t flags, uint8_t* outStatus, double* outT, double* outXyz,
+                         double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = castArgumentError(flags, iso, tol, maxIter, maxCells, n, origins, dirs, tMax, outStatus)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (n == 0) return HPSDF_OK;
+    if (n <= kHostRays && smallQueriesOnHost()) {
+        if (const int hc = t->hostCopies()) return hc;
+        const int left = reductionLeftAssoc(ctx);
+        const CastArgs a{iso, tol, maxIter, maxCells, flags, 0u};
+        for (size_t i = 0; i < n; ++i)
+            hostCastRay(*t, origins + 3 * i, dirs + 3 * i, tMax[i], a, left, outStatus + i, outT ? outT + i : nullptr,
+                        outXyz ? outXyz + 3 * i : nullptr, outVal ? outVal + i : nullptr, outGrad ? outGrad + 3 * i : nullptr,
+                        outEvals ? outEvals + i : nullptr, outCells ? outCells + i : nullptr);
+        return HPSDF_OK;
+    }
+    // the three inputs and the status first, then the optional outputs asked for
+    HostArray arr[10] = {{origins, nullptr, n * 3 * sizeof(double)}, {dirs, nullptr, n * 3 * sizeof(double)}, {tMax, nullptr, n * sizeof(double)},
+                         {nullptr, outStatus, n}};
+    int used = 4, iT = -1, iXyz = -1, iVal = -1, iGrad = -1, iEvals = -1, iCells = -1;
+    if (outT) arr[iT = used++] = HostArray{nullptr, outT, n * sizeof(double)};
+    if (outXyz) arr[iXyz = used++] = HostArray{nullptr, outXyz, n * 3 * sizeof(double)};
+    if (outVal) arr[iVal = used++] = HostArray{nullptr, outVal, n * sizeof(double)};
+    if (outGrad) arr[iGrad = used++] = HostArray{nullptr, outGrad, n * 3 * sizeof(double)};
+    if (outEvals) arr[iEvals = used++] = HostArray{nullptr, outEvals, n * sizeof(uint16_t)};
+    if (outCells) arr[iCells = used++] = HostArray{nullptr, outCells, n * sizeof(uint16_t)};
+    return hostCall(ctx, arr, used, [&] {
+        return hpsdf_cast_rays_device(ctx, t, (const double*)arr[0].dev, (const double*)arr[1].dev, (const double*)arr[2].dev, n, iso, tol, maxIter,
+                                      maxCells, flags, (uint8_t*)arr[3].dev, iT < 0 ? nullptr : (double*)arr[iT].dev,
+                                      iXyz < 0 ? nullptr : (double*)arr[iXyz].dev, iVal < 0 ? nullptr : (double*)arr[iVal].dev,
+                                      iGrad < 0 ? nullptr : (double*)arr[iGrad].dev, iEvals < 0 ? nullptr : (uint16_t*)arr[iEvals].dev,
+                                      iCells < 0 ? nullptr : (uint16_t*)arr[iCells].dev);
     });
     HPSDF_CATCH
 }

@@ -20,6 +20,7 @@
 #include "block.hpp"
 #include "leaf_gradient.hpp"
 #include "leaf_hessian.hpp"
+#include "ray_cast.hpp"
 #include "runtime.hpp"
 #include "tables.hpp"
 
@@ -266,6 +267,69 @@ int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIte
 
 namespace {
 
+// what castRay (ray_cast.hpp) needs of a tree on the calling thread: QueryGradient at a world point, and the box of the leaf that
+// Query's descent reaches from a point of the unit cube (descend's loop; the boxes are the exact dyadics it recomputes)
+struct HostCastField {
+    const hpsdf_tree& t;
+    int leftAssoc;
+    double eval(const double (&x)[3], double (&g)[3]) const {
+        double f;
+        hostQueryPointTrueGradient(t, x, false, leftAssoc, &f, g);
+        return f;
+    }
+    void locate(const double (&pu)[3], double (&lo)[3], double (&hi)[3], int& degree) const {
+        double c[3] = {0.0, 0.0, 0.0}, q = 0.25;
+        const NodeRec* nodes = t.hRecs.data();
+        uint64_t idx = 0;
+        while (nodes[idx].b == kInteriorTag) {
+            uint64_t next = nodes[idx].a;
+            for (int a = 0; a < 3; ++a) {
+                const bool up = pu[a] >= c[a];
+                next += up ? (1ull << a) : 0ull;
+                c[a] = up ? c[a] + q : c[a] - q;
+            }
+            q = q * 0.5;
+            idx = next;
+        }
+        const double h = q + q;
+        for (int a = 0; a < 3; ++a) lo[a] = c[a] - h, hi[a] = c[a] + h;
+        degree = (int)nodes[idx].b;
+    }
+};
+
+inline uint16_t saturate16(uint32_t v) { return (uint16_t)(v > 65535u ? 65535u : v); }
+
+}  // namespace
+
+// CastRays (include/hpsdf.h) for one ray: castRay (ray_cast.hpp) over the routines above.  Every output but outStatus may be null.
+void hostCastRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, const CastArgs& a, int leftAssoc, uint8_t* outStatus,
+                 double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells) {
+    HostCastField F{t, leftAssoc};
+    CastRow r;
+    castRay(F, t.dev.rootCentre, t.dev.rootInvSizes, leftAssoc, origin, dir, tMax, a, r);
+    *outStatus = (uint8_t)r.status;
+    if (outT) *outT = r.t;
+    if (outXyz) outXyz[0] = r.x[0], outXyz[1] = r.x[1], outXyz[2] = r.x[2];
+    if (outVal) *outVal = r.f;
+    if (outGrad) outGrad[0] = r.g[0], outGrad[1] = r.g[1], outGrad[2] = r.g[2];
+    if (outEvals) *outEvals = saturate16(r.evals);
+    if (outCells) *outCells = saturate16(r.cells);
+}
+
+// what hpsdf_cast_rays_* reject before anything runs (0: fine)
+int castArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter, uint32_t maxCells, size_t n, const void* origins, const void* dirs,
+                      const void* tMax, const void* outStatus) {
+    if (flags & ~HPSDF_CAST_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_cast_rays: unknown flag bits");
+    if (!(tol >= 0.0)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_cast_rays: tol must be >= 0");
+    if (!std::isfinite(iso)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_cast_rays: iso must be finite");
+    if (maxIter > 255u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_cast_rays: max_iter must be <= 255");
+    if (maxCells < 1u || maxCells > 65535u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_cast_rays: max_cells must be in 1..65535");
+    if (n && (!origins || !dirs || !tMax || !outStatus)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    return HPSDF_OK;
+}
+
+namespace {
+
 // A serialised block as a host-only tree handle: validated and laid out like the device mirror (block.hpp), so the descent and the
 // evaluation are the code above.
 int treeFromBlock(const void* block, size_t size, hpsdf_tree& t) {
@@ -333,6 +397,26 @@ extern "C" int hpsdf_project_block(const void* block, size_t size, const double*
         hostProjectPoint(t, xyz + 3 * i, iso, tol, max_iter, (flags & HPSDF_PROJECT_UNIT) != 0u, left, out_xyz + 3 * i,
                          out_val ? out_val + i : nullptr, out_grad ? out_grad + 3 * i : nullptr, out_iters ? out_iters + i : nullptr,
                          out_status ? out_status + i : nullptr);
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+// CastRays from a serialised block, on the calling thread (no device; the process-wide reduction order)
+extern "C" int hpsdf_cast_rays_block(const void* block, size_t size, const double* origins, const double* dirs, const double* t_max, size_t n,
+                                     double iso, double tol, uint32_t max_iter, uint32_t max_cells, uint32_t flags, uint8_t* out_status,
+                                     double* out_t, double* out_xyz, double* out_val, double* out_grad, uint16_t* out_evals,
+                                     uint16_t* out_cells) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (const int rc = castArgumentError(flags, iso, tol, max_iter, max_cells, n, origins, dirs, t_max, out_status)) return rc;
+    hpsdf_tree t;
+    if (const int rc = treeFromBlock(block, size, t)) return rc;
+    const int left = reductionLeftAssoc(nullptr);
+    const CastArgs a{iso, tol, max_iter, max_cells, flags, 0u};
+    for (size_t i = 0; i < n; ++i)
+        hostCastRay(t, origins + 3 * i, dirs + 3 * i, t_max[i], a, left, out_status + i, out_t ? out_t + i : nullptr,
+                    out_xyz ? out_xyz + 3 * i : nullptr, out_val ? out_val + i : nullptr, out_grad ? out_grad + 3 * i : nullptr,
+                    out_evals ? out_evals + i : nullptr, out_cells ? out_cells + i : nullptr);
     return HPSDF_OK;
     HPSDF_CATCH
 }

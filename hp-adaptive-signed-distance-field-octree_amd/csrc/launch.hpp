@@ -47,6 +47,11 @@ struct ProjectArgs {
 };
 hipError_t launchProject(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n, const ProjectArgs& a,
                          double* dOutXyz, double* dOutVal, double* dOutGrad, uint8_t* dOutIters, uint8_t* dOutStatus);
+// ---- CastRays (cast_rays.hip): the first crossing of each ray with {Query = iso}; every output but dOutStatus may be null
+struct CastArgs;  // ray_cast.hpp
+hipError_t launchCastRays(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dOrigins, const double* dDirs,
+                          const double* dTMax, size_t n, const CastArgs& a, uint8_t* dOutStatus, double* dOutT, double* dOutXyz, double* dOutVal,
+                          double* dOutGrad, uint16_t* dOutEvals, uint16_t* dOutCells);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

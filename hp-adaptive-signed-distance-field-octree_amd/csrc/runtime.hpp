@@ -231,6 +231,13 @@ int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const doub
 void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc, double* outXyz,
                       double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus);
 int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter);
+// CastRays of one ray on the calling thread (host_query.cpp; the statements are ray_cast.hpp's): the kernels' rows bit for bit; every
+// output but outStatus may be null.  castArgumentError: the argument checks the three hpsdf_cast_rays_* entries share (sets the message)
+struct CastArgs;
+void hostCastRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, const CastArgs& a, int leftAssoc, uint8_t* outStatus,
+                 double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells);
+int castArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter, uint32_t maxCells, size_t n, const void* origins, const void* dirs,
+                      const void* tMax, const void* outStatus);
 
 // innermost non-CSG field and the FieldDev the kernels take
 const hpsdf_field* innermost(const hpsdf_field* f);

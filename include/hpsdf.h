@@ -429,6 +429,83 @@ HPSDF_API int hpsdf_project_block(const void* block, size_t size, const double* 
 HPSDF_API int hpsdf_surface_project_vertices(hpsdf_ctx* ctx, const hpsdf_tree* t, double* verts, uint64_t nv, const double h[3], double iso,
                                              double tol, uint32_t max_iter, uint64_t* n_moved);
 
+/* ---- CastRays: the first crossing of a ray with the level set {Query = iso} (no reference counterpart; hpsdf_query_ray_* below stays
+ * the reference's sphere tracing, statement by statement).  The field is a polynomial of total degree <= p inside a leaf, hence a
+ * polynomial of degree <= p in the ray parameter there: the ray is walked leaf by leaf, sampled max(1, p) times per leaf segment, and
+ * the first sign change of Query - iso is refined by a safeguarded Newton iteration on the polynomial's own directional derivative.
+ * There is no distance-field (Lipschitz) assumption and no fixed epsilon.
+ * Per ray: a world origin o[3], a world direction d[3] used as it is (t is in units of |d|), t_max; per call iso (finite), tol (>= 0,
+ * not NaN), max_iter (0..255), max_cells (1..65535).  Host, device and block entries run the same statements (csrc/ray_cast.hpp; no
+ * fused multiply-add anywhere) and give the same bits.  With
+ *     x(t)_a = o_a + t d_a                       (one multiply, one add)
+ *     (f, g)(t) = QueryGradient(x(t)), the world gradient, not normalised;   r(t) = f - iso
+ *     s(t) = sum3(g_0 d_0, g_1 d_1, g_2 d_2),  sum3(a,b,c) = a + (b + c), or (a + b) + c under hpsdf_[ctx_]set_reduction_order(1)
+ *     below(v) = the largest double less than v
+ *   1 validity   a non-finite o_a or d_a, d = 0 on all axes, t_max NaN or negative:                    status = HPSDF_CAST_INVALID
+ *   2 clip       ou_a = (o_a - rootCentre_a) rootInvSizes_a;  du_a = d_a rootInvSizes_a;  t0 = 0;  t1 = t_max;  per axis a = 0, 1, 2:
+ *                  du_a == 0:  if !(-0.5 <= ou_a <= 0.5):                                              status = HPSDF_CAST_MISS
+ *                  else  tl = (-0.5 - ou_a) / du_a,  th = (0.5 - ou_a) / du_a;  (tin, tout) = du_a > 0 ? (tl, th) : (th, tl)
+ *                        if tin > t0: t0 = tin;   if tout < t1: t1 = tout
+ *                if !(t0 <= t1):                                                                       status = HPSDF_CAST_MISS
+ *   3 first      te = t0; evaluate (every evaluation counts one in out_evals):
+ *                  f == DBL_MAX (the point rounded outside the root):                                  status = HPSDF_CAST_MISS
+ *                  prev = r(t0), t_prev = t0;  fabs(prev) <= tol:                                      status = HPSDF_CAST_HIT at t0
+ *   4 walk       pu_a = ou_a + t0 du_a (the product first) clamped into [-0.5, 0.5];  Query's descent of pu gives the leaf: its box
+ *                [lo_a, hi_a] (exact dyadics) and degree p;  cells = 1;  t = t0.  Then repeat:
+ *       exit     over the axes with du_a != 0 in the order 0, 1, 2:  face_a = du_a > 0 ? hi_a : lo_a,  ta = (face_a - ou_a) / du_a;
+ *                tb = the smallest ta, e = the first axis attaining it (no such axis: tb = t1, and the move below is a MISS);
+ *                if !(tb >= t): tb = t;   if !(tb <= t1): tb = t1
+ *       samples  if tb > t:  S = max(1, p);  for j = 1..S:  t_j = t + (tb - t) ((double)j / (double)S), and t_S = tb itself;
+ *                  f == DBL_MAX:                                                                       status = HPSDF_CAST_MISS
+ *                  cur = r(t_j);  fabs(cur) <= tol:                                                    status = HPSDF_CAST_HIT at t_j
+ *                  (prev < 0) != (cur < 0):  refine the bracket [t_prev, t_j] (step 5)
+ *                  else prev = cur, t_prev = t_j
+ *       end      if tb >= t1:                                                                          status = HPSDF_CAST_MISS
+ *       move     across face e:  du_e > 0 and hi_e >= 0.5, or du_e < 0 and lo_e <= -0.5 (the root's own face):  status = HPSDF_CAST_MISS
+ *                if cells == max_cells:                                                                status = HPSDF_CAST_CELL_LIMIT
+ *                pu_e = du_e > 0 ? hi_e : below(lo_e)      (the descent's >= takes the upper cell at the face itself)
+ *                pu_a = ou_a + tb du_a clamped into [lo_a, below(hi_a)] on the other two axes
+ *                descend pu to the next leaf;  cells = cells + 1;  t = tb
+ *                Every move crosses one cell face in the direction of travel, so the walk always advances.
+ *   5 refine     [a, b] = [t_prev, t_j]: r(a) and r(b) of opposite sign, neither within tol.  c = b;  k = 0;  halved = true.  Repeat:
+ *                  tn = c - r(c) / s(c);   m = tn if halved and a < tn < b, else a + 0.5 (b - a)
+ *                  if !(a < m < b) or k == max_iter:                                                   status = HPSDF_CAST_UNCONVERGED at b
+ *                  evaluate at m;  f == DBL_MAX:                                                       status = HPSDF_CAST_UNCONVERGED at b
+ *                  fabs(r(m)) <= tol:                                                                  status = HPSDF_CAST_HIT at m
+ *                  w = b - a;  the end of the bracket whose r has the sign of r(m) (sign: r < 0) becomes m;  c = m
+ *                  halved = (b - a) <= 0.5 w;   k = k + 1
+ * HPSDF_CAST_UNCONVERGED is an outcome, not an error: the field jumps across cell faces, and a sign change can sit on a jump wider
+ * than tol; the row then holds the upper end of the last bracket (the first sample behind the crossing).
+ * Outputs per ray; out_status is required, every other output optional (NULL):
+ *   out_status   uint8_t, HPSDF_CAST_*
+ *   out_t        the parameter of the row; a quiet NaN for MISS, INVALID and CELL_LIMIT
+ *   out_xyz[3]   x(out_t); quiet NaNs where out_t is one
+ *   out_val, out_grad[3]   QueryGradient(out_xyz) bit for bit (DBL_MAX and quiet NaNs where out_xyz is NaN); under HPSDF_CAST_UNIT the
+ *                gradient is normalised as HPSDF_GRADIENT_UNIT normalises it
+ *   out_evals    uint16_t, field evaluations spent (saturating at 65535);   out_cells   uint16_t, leaves visited
+ * Limits: two crossings closer together than one sample interval (a grazing ray) are not seen; a crossing that exists only as a jump
+ * across a cell face is reported as HPSDF_CAST_UNCONVERGED; the samples are placed by the walk's own arithmetic, while each one is
+ * evaluated by the ordinary descent of x(t), so a sample within rounding of a cell face may be answered by the neighbouring leaf.
+ * Unknown flag bits, a NULL tree, NULL origins, dirs, t_max or out_status with n > 0, tol negative or NaN, a non-finite iso,
+ * max_iter > 255, max_cells outside 1..65535: HPSDF_ERR_INVALID_ARGUMENT, and no output is written.  n == 0 is HPSDF_OK.  _device is
+ * asynchronous on the context stream; _host answers calls of up to 32 rays on the calling thread and sends larger ones through the
+ * device; _block needs no device: it works from a serialised block on the calling thread under the process-wide reduction order, and
+ * accepts and refuses blocks as hpsdf_project_block does. */
+#define HPSDF_CAST_UNIT 1u
+enum { HPSDF_CAST_HIT = 0, HPSDF_CAST_MISS = 1, HPSDF_CAST_UNCONVERGED = 2, HPSDF_CAST_CELL_LIMIT = 3, HPSDF_CAST_INVALID = 4 };
+HPSDF_API int hpsdf_cast_rays_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_origins, const double* d_dirs, const double* d_t_max,
+                                     size_t n, double iso, double tol, uint32_t max_iter, uint32_t max_cells, uint32_t flags,
+                                     uint8_t* d_out_status, double* d_out_t, double* d_out_xyz, double* d_out_val, double* d_out_grad,
+                                     uint16_t* d_out_evals, uint16_t* d_out_cells);
+HPSDF_API int hpsdf_cast_rays_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* origins, const double* dirs, const double* t_max, size_t n,
+                                   double iso, double tol, uint32_t max_iter, uint32_t max_cells, uint32_t flags, uint8_t* out_status,
+                                   double* out_t, double* out_xyz, double* out_val, double* out_grad, uint16_t* out_evals,
+                                   uint16_t* out_cells);
+HPSDF_API int hpsdf_cast_rays_block(const void* block, size_t size, const double* origins, const double* dirs, const double* t_max, size_t n,
+                                    double iso, double tol, uint32_t max_iter, uint32_t max_cells, uint32_t flags, uint8_t* out_status,
+                                    double* out_t, double* out_xyz, double* out_val, double* out_grad, uint16_t* out_evals,
+                                    uint16_t* out_cells);
+
 /* Octree::QueryRay (Octree.cpp:705-746; Ray: Include/HP/Ray.h, Source/HP/Ray.cpp:5-68) for n rays: sphere
  * tracing, <= 200 Query steps each.  hit[i] = 1/0; t[i] is written only on a hit (the reference leaves t_
  * untouched otherwise) and receives what the reference stores there -- the field value at the stopping point

@@ -632,6 +632,35 @@ class Octree {
         return moved;
     }
 
+    /// Where ray_ (origin + t * direction, the direction used as given, t in [0, tMax_]) first crosses the level set {Query = iso_}
+    /// (no reference counterpart; include/hpsdf.h, "CastRays").  Unlike QueryRay -- the reference's sphere tracing -- t_ is the ray
+    /// parameter and a hit lies within tol_ of the level set.  Returns the status: HPSDF_CAST_HIT, _MISS, _UNCONVERGED (a sign change
+    /// that sits on a jump across a cell face: t_ is the first sample behind it), _CELL_LIMIT or _INVALID; t_ is NaN for MISS,
+    /// CELL_LIMIT and INVALID.  point_, value_ and gradient_ (QueryGradient at the point; unit_: normalised) are optional
+    int CastRay(const Ray& ray_, const f64 tMax_, f64& t_, Eigen::Vector3d* point_ = nullptr, Eigen::Vector3d* gradient_ = nullptr, f64 iso_ = 0.0,
+                f64 tol_ = 1e-9, uint32_t maxIter_ = 32, uint32_t maxCells_ = 4096, bool unit_ = false, f64* value_ = nullptr) const {
+        const double o[3] = {ray_.origin(0), ray_.origin(1), ray_.origin(2)};
+        const double d[3] = {ray_.direction(0), ray_.direction(1), ray_.direction(2)};
+        double t = 0.0, x[3] = {0.0, 0.0, 0.0}, val = 0.0, g[3] = {0.0, 0.0, 0.0};
+        uint8_t st = 0;
+        CastRays(o, d, &tMax_, 1, &st, &t, x, &val, g, nullptr, nullptr, iso_, tol_, maxIter_, maxCells_, unit_);
+        t_ = t;
+        if (point_) *point_ = Eigen::Vector3d(x[0], x[1], x[2]);
+        if (value_) *value_ = val;
+        if (gradient_) *gradient_ = Eigen::Vector3d(g[0], g[1], g[2]);
+        return st;
+    }
+    /// Batched form over host arrays (3, 3 and 1 doubles a ray); every output but outStatus may be null
+    void CastRays(const double* origins, const double* dirs, const double* tMax, usize n, uint8_t* outStatus, double* outT = nullptr,
+                  double* outXyz = nullptr, double* outVal = nullptr, double* outGrad = nullptr, uint16_t* outEvals = nullptr,
+                  uint16_t* outCells = nullptr, f64 iso_ = 0.0, f64 tol_ = 1e-9, uint32_t maxIter_ = 32, uint32_t maxCells_ = 4096,
+                  bool unit_ = false) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        check(hpsdf_cast_rays_host(ctx_, t, origins, dirs, tMax, n, iso_, tol_, maxIter_, maxCells_, unit_ ? HPSDF_CAST_UNIT : 0u, outStatus, outT,
+                                   outXyz, outVal, outGrad, outEvals, outCells));
+    }
+
     /// Returns the aabb of the root node   (Octree.h:81)
     Eigen::AlignedBox3f GetRootAABB() const { return config_.root; }
 
