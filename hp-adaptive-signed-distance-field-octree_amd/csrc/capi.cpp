@@ -20,6 +20,7 @@
 #include "continuity.hpp"
 #include "frontier.hpp"
 #include "block.hpp"
+#include "host_call.hpp"
 #include "launch.hpp"
 #include "ray_cast.hpp"
 #include "runtime.hpp"
@@ -157,89 +158,13 @@ int makeFieldDev(const hpsdf_ctx* ctx, const hpsdf_field* f, const double* dSamp
 
 }  // namespace hpsdf
 
-// ---- host-array entry points: cached device + pinned scratch ---------------------------------------------
 namespace {
-constexpr size_t kPinnedPathBytes = 1u << 20;  // below this, user memory is staged through the pinned buffer
-constexpr size_t kZeroCopyBytes = 4096;        // below this the kernel works on the pinned buffer itself: a scalar
-                                               // Query(pt) then costs a launch and a wait, not two copies as well
-inline size_t alignUp(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int ensureHostScratch(hpsdf_ctx* ctx, size_t devBytes, size_t pinBytes) {
-    if (ctx->hostDevCap < devBytes) {
-        if (ctx->hostDev) HPSDF_HIP(hipFree(ctx->hostDev));
-        ctx->hostDev = nullptr;
-        ctx->hostDevCap = 0;
-        size_t cap = 1u << 16;
-        while (cap < devBytes) cap *= 2;
-        HPSDF_HIP(hipMalloc((void**)&ctx->hostDev, cap));
-        ctx->hostDevCap = cap;
-    }
-    if (ctx->hostPinCap < pinBytes) {
-        if (ctx->hostPin) HPSDF_HIP(hipHostFree(ctx->hostPin));
-        ctx->hostPin = nullptr;
-        ctx->hostPinCap = 0;
-        size_t cap = 1u << 16;
-        while (cap < pinBytes) cap *= 2;
-        HPSDF_HIP(hipHostMalloc((void**)&ctx->hostPin, cap, hipHostMallocDefault));
-        ctx->hostPinCap = cap;
-        void* dp = nullptr;
-        ctx->hostPinDev = hipHostGetDevicePointer(&dp, ctx->hostPin, 0) == hipSuccess ? (char*)dp : nullptr;
-    }
-    return HPSDF_OK;
-}
-
-// One host call: `ins` are copied to the device, `run` launches on the context stream, `outs` come back.
-// inout arrays are both (rows the kernel leaves untouched keep the caller's values).
-struct HostArray {
-    const void* src;  // host source (nullptr: output only)
-    void* dst;        // host destination (nullptr: input only)
-    size_t bytes;
-    char* dev = nullptr;
-};
-template <typename Run>
-int hostCall(hpsdf_ctx* ctx, HostArray* arrays, int nArrays, Run&& run) {
-    std::lock_guard<std::mutex> guard(ctx->hostLock);
+// "This tree on this context, ready to launch", the prologue of the *_device entries that take a tree: a tree of another device is refused,
+// the context's device becomes the current one, *td (if asked for) is the tree as the kernels take it, in the context's reduction order.
+int treeOnContext(hpsdf_ctx* ctx, const hpsdf_tree* t, TreeDev* td = nullptr) {
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
     HPSDF_HIP(hipSetDevice(ctx->device));
-    size_t total = 0;
-    for (int a = 0; a < nArrays; ++a) total += alignUp(arrays[a].bytes);
-    const bool staged = total <= kPinnedPathBytes;
-    int rc = ensureHostScratch(ctx, total, staged ? total : 0);
-    if (rc) return rc;
-    static const bool zeroCopyOff = std::getenv("HPSDF_NO_ZEROCOPY") != nullptr;  // measurement knob
-    const bool zeroCopy = total <= kZeroCopyBytes && ctx->hostPinDev != nullptr && !zeroCopyOff;
-    size_t off = 0;
-    for (int a = 0; a < nArrays; ++a) {
-        arrays[a].dev = zeroCopy ? ctx->hostPinDev + off : ctx->hostDev + off;
-        if (arrays[a].src) {
-            const void* from = arrays[a].src;
-            if (staged) {
-                std::memcpy(ctx->hostPin + off, arrays[a].src, arrays[a].bytes);
-                from = ctx->hostPin + off;
-            }
-            if (!zeroCopy) HPSDF_HIP(hipMemcpyAsync(arrays[a].dev, from, arrays[a].bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        off += alignUp(arrays[a].bytes);
-    }
-    rc = run();
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    off = 0;
-    for (int a = 0; a < nArrays; ++a) {
-        if (arrays[a].dst && !zeroCopy)
-            HPSDF_HIP(hipMemcpyAsync(staged ? (void*)(ctx->hostPin + off) : arrays[a].dst, arrays[a].dev, arrays[a].bytes,
-                                     hipMemcpyDeviceToHost, ctx->stream));
-        off += alignUp(arrays[a].bytes);
-    }
-    HPSDF_HIP(hipStreamSynchronize(ctx->stream));
-    if (staged) {
-        off = 0;
-        for (int a = 0; a < nArrays; ++a) {
-            if (arrays[a].dst) std::memcpy(arrays[a].dst, ctx->hostPin + off, arrays[a].bytes);
-            off += alignUp(arrays[a].bytes);
-        }
-    }
+    if (td) *td = t->dev, td->leftAssoc = reductionLeftAssoc(ctx);
     return HPSDF_OK;
 }
 }  // namespace
@@ -632,8 +557,10 @@ int hpsdf_field_eval_device(hpsdf_ctx* ctx, const hpsdf_field* f, const double* 
 static int hostRoundTrip(hpsdf_ctx* ctx, const double* xyz, size_t n, double* out,
                          int (*run)(hpsdf_ctx*, const void*, const double*, size_t, double*), const void* obj) {
     if (n == 0) return HPSDF_OK;
-    HostArray arr[2] = {{xyz, nullptr, n * 3 * sizeof(double)}, {nullptr, out, n * sizeof(double)}};
-    return hostCall(ctx, arr, 2, [&] { return run(ctx, obj, (const double*)arr[0].dev, n, (double*)arr[1].dev); });
+    HostArrays arr;
+    const auto dXyz = arr.in(xyz, n * 3);
+    const auto dOut = arr.out(out, n);
+    return hostCall(ctx, arr, [&] { return run(ctx, obj, dXyz, n, dOut); });
 }
 
 // Up to how many points / rays a *_host call is answered on the calling thread.  The defaults are where the two paths cost the same on an
@@ -804,9 +731,10 @@ int hpsdf_selftest_acosf(hpsdf_ctx* ctx, uint32_t first_bits, uint32_t stride, s
     if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
     if (!out && n) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HPSDF_OK;
-    HostArray arr[1] = {{nullptr, out, n * sizeof(float)}};
-    return hostCall(ctx, arr, 1, [&] {
-        HPSDF_HIP(launchAcosfSelftest(ctx->stream, first_bits, stride, n, (float*)arr[0].dev));
+    HostArrays arr;
+    const auto dOut = arr.out(out, n);
+    return hostCall(ctx, arr, [&] {
+        HPSDF_HIP(launchAcosfSelftest(ctx->stream, first_bits, stride, n, dOut));
         return (int)HPSDF_OK;
     });
     HPSDF_CATCH
@@ -920,8 +848,8 @@ int hpsdf_tree_info(const hpsdf_tree* t, uint64_t* nNodes, uint64_t* nCoeffs, ui
 
 // Query / QueryWithGradient over device arrays (dGrad == nullptr: values only)
 static int queryDevice(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz, size_t n, double* dOut, double* dGrad) {
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
+    TreeDev td;
+    if (const int rc = treeOnContext(ctx, t, &td)) return rc;
     const size_t kChunk = (size_t)1 << 31;  // deferred indices are 32-bit
     for (size_t off = 0; off < n; off += kChunk) {
         const size_t m = std::min(kChunk, n - off);
@@ -941,8 +869,6 @@ static int queryDevice(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz, 
                 ctx->deferCap = need;
             }
         }
-        TreeDev td = t->dev;
-        td.leftAssoc = reductionLeftAssoc(ctx);
         HPSDF_HIP(launchQuery(ctx->stream, td, ctx->dTables, dXyz + 3 * off, m, dOut + off, dGrad ? dGrad + 3 * off : nullptr,
                               t->allInline, ctx->dDeferCount, ctx->dDefer));
     }
@@ -996,11 +922,11 @@ int hpsdf_query_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double*
         return HPSDF_OK;
     }
     // rows of points outside the root keep what the caller passed in (the reference leaves its output untouched)
-    HostArray arr[3] = {{xyz, nullptr, n * 3 * sizeof(double)}, {nullptr, out, n * sizeof(double)}, {grad, grad, n * 3 * sizeof(double)}};
-    return hostCall(ctx, arr, 3, [&] {
-        return hpsdf_query_gradient_device(ctx, t, (const double*)arr[0].dev, n, (double*)arr[1].dev, (double*)arr[2].dev);
-    });
-    return HPSDF_OK;
+    HostArrays arr;
+    const auto dXyz = arr.in(xyz, n * 3);
+    const auto dOut = arr.out(out, n);
+    const auto dGrad = arr.inout(grad, n * 3);
+    return hostCall(ctx, arr, [&] { return hpsdf_query_gradient_device(ctx, t, dXyz, n, dOut, dGrad); });
     HPSDF_CATCH
 }
 
@@ -1012,10 +938,8 @@ int hpsdf_query_true_gradient_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const 
     if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_true_gradient: unknown flag bits");
     if (!t || (n && (!dXyz || !dGrad))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HPSDF_OK;
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
-    TreeDev td = t->dev;
-    td.leftAssoc = reductionLeftAssoc(ctx);
+    TreeDev td;
+    if (const int rc = treeOnContext(ctx, t, &td)) return rc;
     HPSDF_HIP(launchQueryTrueGradient(ctx->stream, td, ctx->dTables, dXyz, n, flags, dOut, dGrad, t->allInline));
     return HPSDF_OK;
     HPSDF_CATCH
@@ -1030,16 +954,14 @@ int hpsdf_query_true_gradient_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const do
     if (n == 0) return HPSDF_OK;
     if (n <= kHostQueryPoints && smallQueriesOnHost()) {
         if (const int hc = t->hostCopies()) return hc;
-        const int left = reductionLeftAssoc(ctx);
-        for (size_t i = 0; i < n; ++i)
-            hostQueryPointTrueGradient(*t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad + 3 * i);
+        hostTrueGradientRows(*t, xyz, n, flags, reductionLeftAssoc(ctx), out, grad);
         return HPSDF_OK;
     }
-    HostArray arr[3] = {{xyz, nullptr, n * 3 * sizeof(double)}, {nullptr, grad, n * 3 * sizeof(double)}, {nullptr, out, n * sizeof(double)}};
-    return hostCall(ctx, arr, out ? 3 : 2, [&] {
-        return hpsdf_query_true_gradient_device(ctx, t, (const double*)arr[0].dev, n, flags, out ? (double*)arr[2].dev : nullptr,
-                                                (double*)arr[1].dev);
-    });
+    HostArrays arr;
+    const auto dXyz = arr.in(xyz, n * 3);
+    const auto dOut = arr.out(out, n);
+    const auto dGrad = arr.out(grad, n * 3);
+    return hostCall(ctx, arr, [&] { return hpsdf_query_true_gradient_device(ctx, t, dXyz, n, flags, dOut, dGrad); });
     HPSDF_CATCH
 }
 
@@ -1051,10 +973,8 @@ int hpsdf_query_hessian_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double
     if (const int rc = hessianArgumentError(flags, dXyz, n, dHess, dCurv)) return rc;
     if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
     if (n == 0) return HPSDF_OK;
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
-    TreeDev td = t->dev;
-    td.leftAssoc = reductionLeftAssoc(ctx);
+    TreeDev td;
+    if (const int rc = treeOnContext(ctx, t, &td)) return rc;
     HPSDF_HIP(launchQueryHessian(ctx->stream, td, ctx->dTables, dXyz, n, flags, dOut, dGrad, dHess, dCurv));
     return HPSDF_OK;
     HPSDF_CATCH
@@ -1069,24 +989,16 @@ int hpsdf_query_hessian_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* 
     if (n == 0) return HPSDF_OK;
     if (n <= kHostQueryPoints && smallQueriesOnHost()) {
         if (const int hc = t->hostCopies()) return hc;
-        const int left = reductionLeftAssoc(ctx);
-        for (size_t i = 0; i < n; ++i)
-            hostQueryPointHessian(*t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr,
-                                  grad ? grad + 3 * i : nullptr, hess ? hess + 6 * i : nullptr, curv ? curv + 2 * i : nullptr);
+        hostHessianRows(*t, xyz, n, flags, reductionLeftAssoc(ctx), out, grad, hess, curv);
         return HPSDF_OK;
     }
-    // the input first, then the outputs asked for
-    HostArray arr[5] = {{xyz, nullptr, n * 3 * sizeof(double)}};
-    int used = 1, iOut = -1, iGrad = -1, iHess = -1, iCurv = -1;
-    if (out) arr[iOut = used++] = HostArray{nullptr, out, n * sizeof(double)};
-    if (grad) arr[iGrad = used++] = HostArray{nullptr, grad, n * 3 * sizeof(double)};
-    if (hess) arr[iHess = used++] = HostArray{nullptr, hess, n * 6 * sizeof(double)};
-    if (curv) arr[iCurv = used++] = HostArray{nullptr, curv, n * 2 * sizeof(double)};
-    return hostCall(ctx, arr, used, [&] {
-        return hpsdf_query_hessian_device(ctx, t, (const double*)arr[0].dev, n, flags, iOut < 0 ? nullptr : (double*)arr[iOut].dev,
-                                          iGrad < 0 ? nullptr : (double*)arr[iGrad].dev, iHess < 0 ? nullptr : (double*)arr[iHess].dev,
-                                          iCurv < 0 ? nullptr : (double*)arr[iCurv].dev);
-    });
+    HostArrays arr;
+    const auto dXyz = arr.in(xyz, n * 3);
+    const auto dOut = arr.out(out, n);
+    const auto dGrad = arr.out(grad, n * 3);
+    const auto dHess = arr.out(hess, n * 6);
+    const auto dCurv = arr.out(curv, n * 2);
+    return hostCall(ctx, arr, [&] { return hpsdf_query_hessian_device(ctx, t, dXyz, n, flags, dOut, dGrad, dHess, dCurv); });
     HPSDF_CATCH
 }
 
@@ -1098,10 +1010,8 @@ int hpsdf_project_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dXyz
     if (const int rc = projectArgumentError(flags, iso, tol, maxIter)) return rc;
     if (!t || (n && (!dXyz || !dOutXyz))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return HPSDF_OK;
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
-    TreeDev td = t->dev;
-    td.leftAssoc = reductionLeftAssoc(ctx);
+    TreeDev td;
+    if (const int rc = treeOnContext(ctx, t, &td)) return rc;
     HPSDF_HIP(launchProject(ctx->stream, td, ctx->dTables, dXyz, n, ProjectArgs{iso, tol, maxIter, flags}, dOutXyz, dOutVal, dOutGrad,
                             dOutIters, dOutStatus));
     return HPSDF_OK;
@@ -1117,24 +1027,19 @@ int hpsdf_project_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* xyz, s
     if (n == 0) return HPSDF_OK;
     if (n <= kHostQueryPoints && smallQueriesOnHost()) {
         if (const int hc = t->hostCopies()) return hc;
-        const int left = reductionLeftAssoc(ctx);
-        for (size_t i = 0; i < n; ++i)
-            hostProjectPoint(*t, xyz + 3 * i, iso, tol, maxIter, (flags & HPSDF_PROJECT_UNIT) != 0u, left, outXyz + 3 * i,
-                             outVal ? outVal + i : nullptr, outGrad ? outGrad + 3 * i : nullptr, outIters ? outIters + i : nullptr,
-                             outStatus ? outStatus + i : nullptr);
+        hostProjectRows(*t, xyz, n, iso, tol, maxIter, flags, reductionLeftAssoc(ctx), outXyz, outVal, outGrad, outIters, outStatus);
         return HPSDF_OK;
     }
-    // the input and the point output have device arrays of their own (outXyz may be xyz); the optional outputs follow, those asked for
-    HostArray arr[6] = {{xyz, nullptr, n * 3 * sizeof(double)}, {nullptr, outXyz, n * 3 * sizeof(double)}};
-    int used = 2, iVal = -1, iGrad = -1, iIters = -1, iStatus = -1;
-    if (outVal) arr[iVal = used++] = HostArray{nullptr, outVal, n * sizeof(double)};
-    if (outGrad) arr[iGrad = used++] = HostArray{nullptr, outGrad, n * 3 * sizeof(double)};
-    if (outIters) arr[iIters = used++] = HostArray{nullptr, outIters, n};
-    if (outStatus) arr[iStatus = used++] = HostArray{nullptr, outStatus, n};
-    return hostCall(ctx, arr, used, [&] {
-        return hpsdf_project_device(ctx, t, (const double*)arr[0].dev, n, iso, tol, maxIter, flags, (double*)arr[1].dev,
-                                    iVal < 0 ? nullptr : (double*)arr[iVal].dev, iGrad < 0 ? nullptr : (double*)arr[iGrad].dev,
-                                    iIters < 0 ? nullptr : (uint8_t*)arr[iIters].dev, iStatus < 0 ? nullptr : (uint8_t*)arr[iStatus].dev);
+    // the input and the point output have device arrays of their own (outXyz may be xyz)
+    HostArrays arr;
+    const auto dXyz = arr.in(xyz, n * 3);
+    const auto dOutXyz = arr.out(outXyz, n * 3);
+    const auto dOutVal = arr.out(outVal, n);
+    const auto dOutGrad = arr.out(outGrad, n * 3);
+    const auto dOutIters = arr.out(outIters, n);
+    const auto dOutStatus = arr.out(outStatus, n);
+    return hostCall(ctx, arr, [&] {
+        return hpsdf_project_device(ctx, t, dXyz, n, iso, tol, maxIter, flags, dOutXyz, dOutVal, dOutGrad, dOutIters, dOutStatus);
     });
     HPSDF_CATCH
 }
@@ -1148,10 +1053,8 @@ int hpsdf_cast_rays_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dO
     if (const int rc = castArgumentError(flags, iso, tol, maxIter, maxCells, n, dOrigins, dDirs, dTMax, dOutStatus)) return rc;
     if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
     if (n == 0) return HPSDF_OK;
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
-    TreeDev td = t->dev;
-    td.leftAssoc = reductionLeftAssoc(ctx);
+    TreeDev td;
+    if (const int rc = treeOnContext(ctx, t, &td)) return rc;
     HPSDF_HIP(launchCastRays(ctx->stream, td, ctx->dTables, dOrigins, dDirs, dTMax, n, CastArgs{iso, tol, maxIter, maxCells, flags, 0u},
                              dOutStatus, dOutT, dOutXyz, dOutVal, dOutGrad, dOutEvals, dOutCells));
     return HPSDF_OK;
@@ -1168,30 +1071,24 @@ int hpsdf_cast_rays_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* orig
     if (n == 0) return HPSDF_OK;
     if (n <= kHostRays && smallQueriesOnHost()) {
         if (const int hc = t->hostCopies()) return hc;
-        const int left = reductionLeftAssoc(ctx);
-        const CastArgs a{iso, tol, maxIter, maxCells, flags, 0u};
-        for (size_t i = 0; i < n; ++i)
-            hostCastRay(*t, origins + 3 * i, dirs + 3 * i, tMax[i], a, left, outStatus + i, outT ? outT + i : nullptr,
-                        outXyz ? outXyz + 3 * i : nullptr, outVal ? outVal + i : nullptr, outGrad ? outGrad + 3 * i : nullptr,
-                        outEvals ? outEvals + i : nullptr, outCells ? outCells + i : nullptr);
+        hostCastRows(*t, origins, dirs, tMax, n, CastArgs{iso, tol, maxIter, maxCells, flags, 0u}, reductionLeftAssoc(ctx), outStatus, outT, outXyz,
+                     outVal, outGrad, outEvals, outCells);
         return HPSDF_OK;
     }
-    // the three inputs and the status first, then the optional outputs asked for
-    HostArray arr[10] = {{origins, nullptr, n * 3 * sizeof(double)}, {dirs, nullptr, n * 3 * sizeof(double)}, {tMax, nullptr, n * sizeof(double)},
-                         {nullptr, outStatus, n}};
-    int used = 4, iT = -1, iXyz = -1, iVal = -1, iGrad = -1, iEvals = -1, iCells = -1;
-    if (outT) arr[iT = used++] = HostArray{nullptr, outT, n * sizeof(double)};
-    if (outXyz) arr[iXyz = used++] = HostArray{nullptr, outXyz, n * 3 * sizeof(double)};
-    if (outVal) arr[iVal = used++] = HostArray{nullptr, outVal, n * sizeof(double)};
-    if (outGrad) arr[iGrad = used++] = HostArray{nullptr, outGrad, n * 3 * sizeof(double)};
-    if (outEvals) arr[iEvals = used++] = HostArray{nullptr, outEvals, n * sizeof(uint16_t)};
-    if (outCells) arr[iCells = used++] = HostArray{nullptr, outCells, n * sizeof(uint16_t)};
-    return hostCall(ctx, arr, used, [&] {
-        return hpsdf_cast_rays_device(ctx, t, (const double*)arr[0].dev, (const double*)arr[1].dev, (const double*)arr[2].dev, n, iso, tol, maxIter,
-                                      maxCells, flags, (uint8_t*)arr[3].dev, iT < 0 ? nullptr : (double*)arr[iT].dev,
-                                      iXyz < 0 ? nullptr : (double*)arr[iXyz].dev, iVal < 0 ? nullptr : (double*)arr[iVal].dev,
-                                      iGrad < 0 ? nullptr : (double*)arr[iGrad].dev, iEvals < 0 ? nullptr : (uint16_t*)arr[iEvals].dev,
-                                      iCells < 0 ? nullptr : (uint16_t*)arr[iCells].dev);
+    HostArrays arr;
+    const auto dOrigins = arr.in(origins, n * 3);
+    const auto dDirs = arr.in(dirs, n * 3);
+    const auto dTMax = arr.in(tMax, n);
+    const auto dOutStatus = arr.out(outStatus, n);
+    const auto dOutT = arr.out(outT, n);
+    const auto dOutXyz = arr.out(outXyz, n * 3);
+    const auto dOutVal = arr.out(outVal, n);
+    const auto dOutGrad = arr.out(outGrad, n * 3);
+    const auto dOutEvals = arr.out(outEvals, n);
+    const auto dOutCells = arr.out(outCells, n);
+    return hostCall(ctx, arr, [&] {
+        return hpsdf_cast_rays_device(ctx, t, dOrigins, dDirs, dTMax, n, iso, tol, maxIter, maxCells, flags, dOutStatus, dOutT, dOutXyz, dOutVal,
+                                      dOutGrad, dOutEvals, dOutCells);
     });
     HPSDF_CATCH
 }
@@ -1231,9 +1128,9 @@ int hpsdf_query_ray_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dO
     HPSDF_TRY
     if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
     if (!t || (n && (!dOrigins || !dDirs || !dTMax || !dHit || !dT))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
-    HPSDF_HIP(launchQueryRay(ctx->stream, t->dev, ctx->dTables, dOrigins, dDirs, dTMax, n, dHit, dT));
+    TreeDev td;  // (query_ray_kernel reads no reduction order)
+    if (const int rc = treeOnContext(ctx, t, &td)) return rc;
+    HPSDF_HIP(launchQueryRay(ctx->stream, td, ctx->dTables, dOrigins, dDirs, dTMax, n, dHit, dT));
     return HPSDF_OK;
     HPSDF_CATCH
 }
@@ -1266,13 +1163,13 @@ int hpsdf_query_ray_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* orig
         return HPSDF_OK;
     }
     // t of a miss keeps the caller's value (the reference leaves t_ untouched)
-    HostArray arr[5] = {{origins, nullptr, n * 3 * sizeof(double)}, {dirs, nullptr, n * 3 * sizeof(double)},
-                        {tMax, nullptr, n * sizeof(double)},        {tOut, tOut, n * sizeof(double)},
-                        {nullptr, hit, n}};
-    return hostCall(ctx, arr, 5, [&] {
-        return hpsdf_query_ray_device(ctx, t, (const double*)arr[0].dev, (const double*)arr[1].dev, (const double*)arr[2].dev, n,
-                                      (uint8_t*)arr[4].dev, (double*)arr[3].dev);
-    });
+    HostArrays arr;
+    const auto dOrigins = arr.in(origins, n * 3);
+    const auto dDirs = arr.in(dirs, n * 3);
+    const auto dTMax = arr.in(tMax, n);
+    const auto dT = arr.inout(tOut, n);
+    const auto dHit = arr.out(hit, n);
+    return hostCall(ctx, arr, [&] { return hpsdf_query_ray_device(ctx, t, dOrigins, dDirs, dTMax, n, dHit, dT); });
     HPSDF_CATCH
 }
 
@@ -1295,8 +1192,7 @@ int hpsdf_function_slice(hpsdf_ctx* ctx, const hpsdf_tree* t, double c, const fl
     if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
     if (!t || !viewMin || !viewMax || !rgb) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     if (nSamples == 0 || nSamples > 32768) return fail(HPSDF_ERR_INVALID_ARGUMENT, "n_samples must be in [1, 32768]");
-    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
-    HPSDF_HIP(hipSetDevice(ctx->device));
+    if (const int rc = treeOnContext(ctx, t)) return rc;
     const size_t total = (size_t)nSamples * nSamples;
     DevBufs bufs;
     double *dV = nullptr, *dP = nullptr;

@@ -158,27 +158,14 @@ hipError_t launchCastRays(hipStream_t stream, const TreeDev& t, const DeviceTabl
                           double* dOutGrad, uint16_t* dOutEvals, uint16_t* dOutCells) {
     if (n == 0) return hipSuccess;
     const CastOut o{dOutStatus, dOutT, dOutXyz, dOutVal, dOutGrad, dOutEvals, dOutCells};
-    if (n <= kQueryFewPoints) {
-        const dim3 fgrid((unsigned)((n + 63) / 64)), fblock(64);
-        if (t.maxDegree <= 2)
-            hipLaunchKernelGGL((cast_rays_few_kernel<2>), fgrid, fblock, 0, stream, t, dTables, dOrigins, dDirs, dTMax, (uint32_t)n, a, o);
-        else if (t.maxDegree <= 3)
-            hipLaunchKernelGGL((cast_rays_few_kernel<3>), fgrid, fblock, 0, stream, t, dTables, dOrigins, dDirs, dTMax, (uint32_t)n, a, o);
-        else if (t.maxDegree <= 5)
-            hipLaunchKernelGGL((cast_rays_few_kernel<5>), fgrid, fblock, 0, stream, t, dTables, dOrigins, dDirs, dTMax, (uint32_t)n, a, o);
+    const PointLaunch l(n);
+    forMaxDegree<2, 3, 5, 12>(t.maxDegree, [&](auto P) {
+        constexpr int MAXP = decltype(P)::value;
+        if (l.few)
+            hipLaunchKernelGGL((cast_rays_few_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dOrigins, dDirs, dTMax, (uint32_t)n, a, o);
         else
-            hipLaunchKernelGGL((cast_rays_few_kernel<12>), fgrid, fblock, 0, stream, t, dTables, dOrigins, dDirs, dTMax, (uint32_t)n, a, o);
-        return hipGetLastError();
-    }
-    const dim3 grid(gridFor(n)), block(256);
-    if (t.maxDegree <= 2)
-        hipLaunchKernelGGL((cast_rays_kernel<2>), grid, block, 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, a, o);
-    else if (t.maxDegree <= 3)
-        hipLaunchKernelGGL((cast_rays_kernel<3>), grid, block, 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, a, o);
-    else if (t.maxDegree <= 5)
-        hipLaunchKernelGGL((cast_rays_kernel<5>), grid, block, 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, a, o);
-    else
-        hipLaunchKernelGGL((cast_rays_kernel<12>), grid, block, 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, a, o);
+            hipLaunchKernelGGL((cast_rays_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, a, o);
+    });
     return hipGetLastError();
 }
 

@@ -34,15 +34,12 @@ struct Leaf {
     double u[3];  // (pt - centre) * (2 << depth), Octree.cpp:862
 };
 
-// Octree.cpp:665-701: root remap, f32 containment (both ends inclusive, NaN fails), mid-plane descent (>= takes the upper child)
-inline bool descend(const hpsdf_tree& t, const double* xyz, Leaf& L) {
-    const double p[3] = {(xyz[0] - t.dev.rootCentre[0]) * t.dev.rootInvSizes[0], (xyz[1] - t.dev.rootCentre[1]) * t.dev.rootInvSizes[1],
-                         (xyz[2] - t.dev.rootCentre[2]) * t.dev.rootInvSizes[2]};
-    const float fx = (float)p[0], fy = (float)p[1], fz = (float)p[2];
-    if (!(fx >= -0.5f && fx <= 0.5f && fy >= -0.5f && fy <= 0.5f && fz >= -0.5f && fz <= 0.5f)) return false;
-    double c[3] = {0.0, 0.0, 0.0}, q = 0.25;  // cell centres are exact dyadics: the mid-planes of the f32 boxes
-    int depth = 0;
-    const NodeRec* nodes = t.hRecs.data();  // (interior: a = first child; leaf: a = offset in the line-aligned coefficient mirror, b = degree)
+// Octree.cpp:675-701, the mid-plane descent from a point p of the unit cube (>= takes the upper child): the record of the leaf it ends
+// in, that leaf's centre in c, a quarter of its edge in q and its depth.  (interior: a = first child; leaf: a = offset in the line-aligned
+// coefficient mirror, b = degree)
+inline const NodeRec& walk(const hpsdf_tree& t, const double* p, double (&c)[3], double& q, int& depth) {
+    c[0] = c[1] = c[2] = 0.0, q = 0.25, depth = 0;  // cell centres are exact dyadics: the mid-planes of the f32 boxes
+    const NodeRec* nodes = t.hRecs.data();
     uint64_t idx = 0;
     while (nodes[idx].b == kInteriorTag) {
         uint64_t next = nodes[idx].a;
@@ -55,9 +52,21 @@ inline bool descend(const hpsdf_tree& t, const double* xyz, Leaf& L) {
         ++depth;
         idx = next;
     }
+    return nodes[idx];
+}
+
+// Octree.cpp:665-701: root remap, f32 containment (both ends inclusive, NaN fails), then the walk
+inline bool descend(const hpsdf_tree& t, const double* xyz, Leaf& L) {
+    const double p[3] = {(xyz[0] - t.dev.rootCentre[0]) * t.dev.rootInvSizes[0], (xyz[1] - t.dev.rootCentre[1]) * t.dev.rootInvSizes[1],
+                         (xyz[2] - t.dev.rootCentre[2]) * t.dev.rootInvSizes[2]};
+    const float fx = (float)p[0], fy = (float)p[1], fz = (float)p[2];
+    if (!(fx >= -0.5f && fx <= 0.5f && fy >= -0.5f && fy <= 0.5f && fz >= -0.5f && fz <= 0.5f)) return false;
+    double c[3], q;
+    int depth;
+    const NodeRec& leaf = walk(t, p, c, q, depth);
     const double s = (double)(2 << depth);
-    L.co = t.hPadded.data() + nodes[idx].a;
-    L.degree = (int)nodes[idx].b;
+    L.co = t.hPadded.data() + leaf.a;
+    L.degree = (int)leaf.b;
     L.depth = depth;
     for (int a = 0; a < 3; ++a) L.u[a] = (p[a] - c[a]) * s;
     return true;
@@ -183,6 +192,8 @@ bool hostQueryRay(const hpsdf_tree& t, const double* origin, const double* dir, 
     return false;
 }
 
+namespace {
+
 // QueryGradient (include/hpsdf.h): Query's descent, then the value and the gradient of the leaf's polynomial with the statements the
 // kernels run (leaf_gradient.hpp; query_gradient.hip).  Outside the root: DBL_MAX and three quiet NaNs.
 void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad) {
@@ -204,8 +215,8 @@ void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool uni
 
 // QueryHessian (include/hpsdf.h): Query's descent, then value, gradient, second derivative and curvature with the statements the kernels
 // run (leaf_hessian.hpp; query_hessian.hip).  Every output may be null.  Outside the root: DBL_MAX and quiet NaNs.
-void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad, double* hess,
-                           double* curv) {
+[[gnu::noinline]] void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad,
+                                             double* hess, double* curv) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     double f = DBL_MAX, g[3] = {nan, nan, nan}, H[6] = {nan, nan, nan, nan, nan, nan}, k[2] = {nan, nan};
     Leaf L;
@@ -227,6 +238,30 @@ void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, in
     if (curv) curv[0] = k[0], curv[1] = k[1];
 }
 
+// row i of an optional output array with `stride` elements a row (null stays null)
+template <typename T>
+inline T* rowOf(T* p, size_t i, size_t stride = 1) {
+    return p ? p + stride * i : nullptr;
+}
+
+}  // namespace
+
+// The rows of a call answered on the calling thread: what the *_host entries (capi.cpp, up to kHostQueryPoints / kHostRays rows) and the
+// *_block entries below run.  The optional outputs are passed as they came in.  The per-row routines with a single caller are kept out of line
+// ([[gnu::noinline]]): compiled into its row loop hostCastRay spilt more of its walk's state, and a one-ray call is what the C++ drop-in's
+// scalar CastRay costs (the instruction counts and the timings: profiles/point_call_plumbing_timing.txt, part B).
+void hostTrueGradientRows(const hpsdf_tree& t, const double* xyz, size_t n, uint32_t flags, int leftAssoc, double* out, double* grad) {
+    for (size_t i = 0; i < n; ++i)
+        hostQueryPointTrueGradient(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, leftAssoc, rowOf(out, i), grad + 3 * i);
+}
+
+void hostHessianRows(const hpsdf_tree& t, const double* xyz, size_t n, uint32_t flags, int leftAssoc, double* out, double* grad, double* hess,
+                     double* curv) {
+    for (size_t i = 0; i < n; ++i)
+        hostQueryPointHessian(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, leftAssoc, rowOf(out, i), rowOf(grad, i, 3), rowOf(hess, i, 6),
+                              rowOf(curv, i, 2));
+}
+
 // what hpsdf_query_hessian_* reject before anything runs (0: fine)
 int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const double* hess, const double* curv) {
     if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_hessian: unknown flag bits");
@@ -235,10 +270,12 @@ int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const doub
     return HPSDF_OK;
 }
 
-// ProjectToSurface (include/hpsdf.h) for one point: the loop of project.hip's projectPoint on the routine above.  xyz and outXyz may be
-// the same three doubles; every output but outXyz may be null.
-void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc, double* outXyz,
-                      double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus) {
+namespace {
+
+// ProjectToSurface (include/hpsdf.h) for one point: the loop of project.hip's projectPoint on hostQueryPointTrueGradient.  xyz and outXyz
+// may be the same three doubles; every output but outXyz may be null.
+[[gnu::noinline]] void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc,
+                                        double* outXyz, double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus) {
     double x[3] = {xyz[0], xyz[1], xyz[2]}, f, g[3];
     uint32_t k = 0;
     int status;
@@ -256,6 +293,15 @@ void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double
     if (outStatus) *outStatus = (uint8_t)status;
 }
 
+}  // namespace
+
+void hostProjectRows(const hpsdf_tree& t, const double* xyz, size_t n, double iso, double tol, uint32_t maxIter, uint32_t flags, int leftAssoc,
+                     double* outXyz, double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus) {
+    for (size_t i = 0; i < n; ++i)
+        hostProjectPoint(t, xyz + 3 * i, iso, tol, maxIter, (flags & HPSDF_PROJECT_UNIT) != 0u, leftAssoc, outXyz + 3 * i, rowOf(outVal, i),
+                         rowOf(outGrad, i, 3), rowOf(outIters, i), rowOf(outStatus, i));
+}
+
 // what hpsdf_project_* reject before anything runs (0: fine)
 int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter) {
     if (flags & ~HPSDF_PROJECT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_project: unknown flag bits");
@@ -268,7 +314,7 @@ int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIte
 namespace {
 
 // what castRay (ray_cast.hpp) needs of a tree on the calling thread: QueryGradient at a world point, and the box of the leaf that
-// Query's descent reaches from a point of the unit cube (descend's loop; the boxes are the exact dyadics it recomputes)
+// Query's descent reaches from a point of the unit cube (descend's walk; the boxes are the exact dyadics it recomputes)
 struct HostCastField {
     const hpsdf_tree& t;
     int leftAssoc;
@@ -278,32 +324,20 @@ struct HostCastField {
         return f;
     }
     void locate(const double (&pu)[3], double (&lo)[3], double (&hi)[3], int& degree) const {
-        double c[3] = {0.0, 0.0, 0.0}, q = 0.25;
-        const NodeRec* nodes = t.hRecs.data();
-        uint64_t idx = 0;
-        while (nodes[idx].b == kInteriorTag) {
-            uint64_t next = nodes[idx].a;
-            for (int a = 0; a < 3; ++a) {
-                const bool up = pu[a] >= c[a];
-                next += up ? (1ull << a) : 0ull;
-                c[a] = up ? c[a] + q : c[a] - q;
-            }
-            q = q * 0.5;
-            idx = next;
-        }
+        double c[3], q;
+        int depth;  // (not needed here; walk is inlined and the count goes with it)
+        degree = (int)walk(t, pu, c, q, depth).b;
         const double h = q + q;
         for (int a = 0; a < 3; ++a) lo[a] = c[a] - h, hi[a] = c[a] + h;
-        degree = (int)nodes[idx].b;
     }
 };
 
 inline uint16_t saturate16(uint32_t v) { return (uint16_t)(v > 65535u ? 65535u : v); }
 
-}  // namespace
-
 // CastRays (include/hpsdf.h) for one ray: castRay (ray_cast.hpp) over the routines above.  Every output but outStatus may be null.
-void hostCastRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, const CastArgs& a, int leftAssoc, uint8_t* outStatus,
-                 double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells) {
+[[gnu::noinline]] void hostCastRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, const CastArgs& a, int leftAssoc,
+                                   uint8_t* outStatus, double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals,
+                                   uint16_t* outCells) {
     HostCastField F{t, leftAssoc};
     CastRow r;
     castRay(F, t.dev.rootCentre, t.dev.rootInvSizes, leftAssoc, origin, dir, tMax, a, r);
@@ -314,6 +348,15 @@ void hostCastRay(const hpsdf_tree& t, const double* origin, const double* dir, d
     if (outGrad) outGrad[0] = r.g[0], outGrad[1] = r.g[1], outGrad[2] = r.g[2];
     if (outEvals) *outEvals = saturate16(r.evals);
     if (outCells) *outCells = saturate16(r.cells);
+}
+
+}  // namespace
+
+void hostCastRows(const hpsdf_tree& t, const double* origins, const double* dirs, const double* tMax, size_t n, const CastArgs& a, int leftAssoc,
+                  uint8_t* outStatus, double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells) {
+    for (size_t i = 0; i < n; ++i)
+        hostCastRay(t, origins + 3 * i, dirs + 3 * i, tMax[i], a, leftAssoc, outStatus + i, rowOf(outT, i), rowOf(outXyz, i, 3), rowOf(outVal, i),
+                    rowOf(outGrad, i, 3), rowOf(outEvals, i), rowOf(outCells, i));
 }
 
 // what hpsdf_cast_rays_* reject before anything runs (0: fine)
@@ -330,9 +373,9 @@ int castArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter, 
 
 namespace {
 
-// A serialised block as a host-only tree handle: validated and laid out like the device mirror (block.hpp), so the descent and the
-// evaluation are the code above.
-int treeFromBlock(const void* block, size_t size, hpsdf_tree& t) {
+// What the *_block entries answer from: a serialised block as a host-only tree handle -- validated and laid out like the device mirror
+// (block.hpp), so the descent and the evaluation are the code above -- and, there being no context, the process-wide reduction order.
+int treeFromBlock(const void* block, size_t size, hpsdf_tree& t, int& leftAssoc) {
     BlockView v;
     BlockMirror m;
     std::string why;
@@ -342,6 +385,7 @@ int treeFromBlock(const void* block, size_t size, hpsdf_tree& t) {
     t.hRecs = std::move(m.recs);
     t.hPadded = std::move(m.padded);
     for (int a = 0; a < 3; ++a) t.dev.rootCentre[a] = m.rootCentre[a], t.dev.rootInvSizes[a] = m.rootInvSizes[a];
+    leftAssoc = reductionLeftAssoc(nullptr);
     return HPSDF_OK;
 }
 
@@ -349,8 +393,8 @@ int treeFromBlock(const void* block, size_t size, hpsdf_tree& t) {
 
 }  // namespace hpsdf
 
-// QueryGradient from a serialised block, on the calling thread: no device, no context (so the reduction order is the process-wide
-// one); treeFromBlock makes the tree the code above walks.
+// QueryGradient from a serialised block, on the calling thread: no device, no context; treeFromBlock makes the tree the rows are
+// answered from.
 extern "C" int hpsdf_query_true_gradient_block(const void* block, size_t size, const double* xyz, size_t n, uint32_t flags, double* out,
                                                double* grad) {
     using namespace hpsdf;
@@ -358,10 +402,9 @@ extern "C" int hpsdf_query_true_gradient_block(const void* block, size_t size, c
     if (flags & ~HPSDF_GRADIENT_UNIT) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_true_gradient: unknown flag bits");
     if (n && (!xyz || !grad)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     hpsdf_tree t;
-    if (const int rc = treeFromBlock(block, size, t)) return rc;
-    const int left = reductionLeftAssoc(nullptr);
-    for (size_t i = 0; i < n; ++i)
-        hostQueryPointTrueGradient(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad + 3 * i);
+    int left;
+    if (const int rc = treeFromBlock(block, size, t, left)) return rc;
+    hostTrueGradientRows(t, xyz, n, flags, left, out, grad);
     return HPSDF_OK;
     HPSDF_CATCH
 }
@@ -373,11 +416,9 @@ extern "C" int hpsdf_query_hessian_block(const void* block, size_t size, const d
     HPSDF_TRY
     if (const int rc = hessianArgumentError(flags, xyz, n, hess, curv)) return rc;
     hpsdf_tree t;
-    if (const int rc = treeFromBlock(block, size, t)) return rc;
-    const int left = reductionLeftAssoc(nullptr);
-    for (size_t i = 0; i < n; ++i)
-        hostQueryPointHessian(t, xyz + 3 * i, (flags & HPSDF_GRADIENT_UNIT) != 0u, left, out ? out + i : nullptr, grad ? grad + 3 * i : nullptr,
-                              hess ? hess + 6 * i : nullptr, curv ? curv + 2 * i : nullptr);
+    int left;
+    if (const int rc = treeFromBlock(block, size, t, left)) return rc;
+    hostHessianRows(t, xyz, n, flags, left, out, grad, hess, curv);
     return HPSDF_OK;
     HPSDF_CATCH
 }
@@ -391,12 +432,9 @@ extern "C" int hpsdf_project_block(const void* block, size_t size, const double*
     if (const int rc = projectArgumentError(flags, iso, tol, max_iter)) return rc;
     if (n && (!xyz || !out_xyz)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     hpsdf_tree t;
-    if (const int rc = treeFromBlock(block, size, t)) return rc;
-    const int left = reductionLeftAssoc(nullptr);
-    for (size_t i = 0; i < n; ++i)
-        hostProjectPoint(t, xyz + 3 * i, iso, tol, max_iter, (flags & HPSDF_PROJECT_UNIT) != 0u, left, out_xyz + 3 * i,
-                         out_val ? out_val + i : nullptr, out_grad ? out_grad + 3 * i : nullptr, out_iters ? out_iters + i : nullptr,
-                         out_status ? out_status + i : nullptr);
+    int left;
+    if (const int rc = treeFromBlock(block, size, t, left)) return rc;
+    hostProjectRows(t, xyz, n, iso, tol, max_iter, flags, left, out_xyz, out_val, out_grad, out_iters, out_status);
     return HPSDF_OK;
     HPSDF_CATCH
 }
@@ -410,13 +448,10 @@ extern "C" int hpsdf_cast_rays_block(const void* block, size_t size, const doubl
     HPSDF_TRY
     if (const int rc = castArgumentError(flags, iso, tol, max_iter, max_cells, n, origins, dirs, t_max, out_status)) return rc;
     hpsdf_tree t;
-    if (const int rc = treeFromBlock(block, size, t)) return rc;
-    const int left = reductionLeftAssoc(nullptr);
-    const CastArgs a{iso, tol, max_iter, max_cells, flags, 0u};
-    for (size_t i = 0; i < n; ++i)
-        hostCastRay(t, origins + 3 * i, dirs + 3 * i, t_max[i], a, left, out_status + i, out_t ? out_t + i : nullptr,
-                    out_xyz ? out_xyz + 3 * i : nullptr, out_val ? out_val + i : nullptr, out_grad ? out_grad + 3 * i : nullptr,
-                    out_evals ? out_evals + i : nullptr, out_cells ? out_cells + i : nullptr);
+    int left;
+    if (const int rc = treeFromBlock(block, size, t, left)) return rc;
+    hostCastRows(t, origins, dirs, t_max, n, CastArgs{iso, tol, max_iter, max_cells, flags, 0u}, left, out_status, out_t, out_xyz, out_val, out_grad,
+                 out_evals, out_cells);
     return HPSDF_OK;
     HPSDF_CATCH
 }

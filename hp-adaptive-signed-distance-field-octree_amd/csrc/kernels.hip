@@ -974,12 +974,9 @@ hipError_t launchQuery(hipStream_t stream, const TreeDev& t, const DeviceTables*
     }
     if (!dGrad && n <= kQueryFewPoints) {
         const dim3 fgrid((unsigned)((n + 63) / 64)), fblock(64);
-        if (t.maxDegree <= 3)
-            hipLaunchKernelGGL((query_few_kernel<3>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, dOut);
-        else if (t.maxDegree <= 5)
-            hipLaunchKernelGGL((query_few_kernel<5>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, dOut);
-        else
-            hipLaunchKernelGGL((query_few_kernel<12>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, dOut);
+        forMaxDegree<3, 5, 12>(t.maxDegree, [&](auto P) {
+            hipLaunchKernelGGL((query_few_kernel<decltype(P)::value>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, dOut);
+        });
         return hipGetLastError();
     }
     const dim3 grid(gridFor(n)), block(256);
@@ -1115,12 +1112,9 @@ hipError_t launchQueryRay(hipStream_t stream, const TreeDev& t, const DeviceTabl
                           const double* dDirs, const double* dTMax, size_t n, uint8_t* dHit, double* dT) {
     if (n == 0) return hipSuccess;
     // the evaluation code for the degrees the tree does not contain is left out (registers, no scratch)
-    if (t.maxDegree <= 3)
-        hipLaunchKernelGGL((query_ray_kernel<3>), dim3(gridFor(n)), dim3(256), 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, dHit, dT);
-    else if (t.maxDegree <= 5)
-        hipLaunchKernelGGL((query_ray_kernel<5>), dim3(gridFor(n)), dim3(256), 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, dHit, dT);
-    else
-        hipLaunchKernelGGL((query_ray_kernel<12>), dim3(gridFor(n)), dim3(256), 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, dHit, dT);
+    forMaxDegree<3, 5, 12>(t.maxDegree, [&](auto P) {
+        hipLaunchKernelGGL((query_ray_kernel<decltype(P)::value>), dim3(gridFor(n)), dim3(256), 0, stream, t, dTables, dOrigins, dDirs, dTMax, n, dHit, dT);
+    });
     return hipGetLastError();
 }
 
@@ -1135,12 +1129,9 @@ hipError_t launchSlicePoints(hipStream_t stream, double c, float minX, float min
 hipError_t launchQueryLattice(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const SurfaceLattice& g, double* dOut) {
     if (g.nPts == 0) return hipSuccess;
     const dim3 grid(gridFor(g.nPts)), block(256);
-    if (t.maxDegree <= 3)
-        hipLaunchKernelGGL((lattice_query_kernel<3>), grid, block, 0, stream, t, dTables, g, dOut);
-    else if (t.maxDegree <= 5)
-        hipLaunchKernelGGL((lattice_query_kernel<5>), grid, block, 0, stream, t, dTables, g, dOut);
-    else
-        hipLaunchKernelGGL((lattice_query_kernel<12>), grid, block, 0, stream, t, dTables, g, dOut);
+    forMaxDegree<3, 5, 12>(t.maxDegree, [&](auto P) {
+        hipLaunchKernelGGL((lattice_query_kernel<decltype(P)::value>), grid, block, 0, stream, t, dTables, g, dOut);
+    });
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "device_types.hpp"
 
@@ -22,6 +23,22 @@ inline unsigned gridFor(size_t n) {
     const size_t cap = capEnv ? capEnv : kQueryMaxGrid;  // grid-stride beyond this (the headline kernel: 512 ... 39 063 workgroups for 10 M points measured, flat from 4096 up)
     return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
+// The degree classes of the per-point kernels: the evaluation code for the degrees a tree does not contain is left out of a class (registers,
+// no scratch).  forMaxDegree<2, 3, 5, 12>(t.maxDegree, f) calls f(std::integral_constant<int, P>()) with the first class P of the list that
+// holds maxDegree (the last one takes whatever is left); f is a generic lambda that launches kernel<decltype(P)::value>.
+template <int P, int... Rest, class F>
+inline void forMaxDegree(int maxDegree, F&& f) {
+    if constexpr (sizeof...(Rest) > 0)
+        if (maxDegree > P) return forMaxDegree<Rest...>(maxDegree, f);
+    f(std::integral_constant<int, P>());
+}
+// The two launches of a point call (QueryGradient, QueryHessian, ProjectToSurface, CastRays): up to kQueryFewPoints rows go to the call's
+// few-point kernel in workgroups of one wave (a row a lane, n as uint32_t), more to its grid-stride kernel in workgroups of 256.
+struct PointLaunch {
+    bool few;
+    dim3 grid, block;
+    explicit PointLaunch(size_t n) : few(n <= kQueryFewPoints), grid(few ? (unsigned)((n + 63) / 64) : gridFor(n)), block(few ? 64u : 256u) {}
+};
 hipError_t launchQuery(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
                        double* dOut, double* dGrad, bool allInline, uint32_t* dDeferCount, uint32_t* dDeferIdx);
 hipError_t launchQueryRay(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dOrigins,

@@ -115,27 +115,14 @@ hipError_t launchProject(hipStream_t stream, const TreeDev& t, const DeviceTable
                          double* dOutXyz, double* dOutVal, double* dOutGrad, uint8_t* dOutIters, uint8_t* dOutStatus) {
     if (n == 0) return hipSuccess;
     const ProjectOut o{dOutXyz, dOutVal, dOutGrad, dOutIters, dOutStatus};
-    if (n <= kQueryFewPoints) {
-        const dim3 fgrid((unsigned)((n + 63) / 64)), fblock(64);
-        if (t.maxDegree <= 2)
-            hipLaunchKernelGGL((project_few_kernel<2>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, a, o);
-        else if (t.maxDegree <= 3)
-            hipLaunchKernelGGL((project_few_kernel<3>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, a, o);
-        else if (t.maxDegree <= 5)
-            hipLaunchKernelGGL((project_few_kernel<5>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, a, o);
+    const PointLaunch l(n);
+    forMaxDegree<2, 3, 5, 12>(t.maxDegree, [&](auto P) {
+        constexpr int MAXP = decltype(P)::value;
+        if (l.few)
+            hipLaunchKernelGGL((project_few_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dXyz, (uint32_t)n, a, o);
         else
-            hipLaunchKernelGGL((project_few_kernel<12>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, a, o);
-        return hipGetLastError();
-    }
-    const dim3 grid(gridFor(n)), block(256);
-    if (t.maxDegree <= 2)
-        hipLaunchKernelGGL((project_kernel<2>), grid, block, 0, stream, t, dTables, dXyz, n, a, o);
-    else if (t.maxDegree <= 3)
-        hipLaunchKernelGGL((project_kernel<3>), grid, block, 0, stream, t, dTables, dXyz, n, a, o);
-    else if (t.maxDegree <= 5)
-        hipLaunchKernelGGL((project_kernel<5>), grid, block, 0, stream, t, dTables, dXyz, n, a, o);
-    else
-        hipLaunchKernelGGL((project_kernel<12>), grid, block, 0, stream, t, dTables, dXyz, n, a, o);
+            hipLaunchKernelGGL((project_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dXyz, n, a, o);
+    });
     return hipGetLastError();
 }
 

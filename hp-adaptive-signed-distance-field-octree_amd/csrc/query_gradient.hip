@@ -148,34 +148,21 @@ __global__ __launch_bounds__(256) void query_true_gradient_top_kernel(TreeDev t,
 hipError_t launchQueryTrueGradient(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dXyz, size_t n,
                                    uint32_t flags, double* dOut, double* dGrad, bool allInline) {
     if (n == 0) return hipSuccess;
-    if (n <= kQueryFewPoints) {
-        const dim3 fgrid((unsigned)((n + 63) / 64)), fblock(64);
-        if (t.maxDegree <= 2)
-            hipLaunchKernelGGL((query_true_gradient_few_kernel<2>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, dOut, dGrad);
-        else if (t.maxDegree <= 3)
-            hipLaunchKernelGGL((query_true_gradient_few_kernel<3>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, dOut, dGrad);
-        else if (t.maxDegree <= 5)
-            hipLaunchKernelGGL((query_true_gradient_few_kernel<5>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, dOut, dGrad);
-        else
-            hipLaunchKernelGGL((query_true_gradient_few_kernel<12>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, dOut, dGrad);
-        return hipGetLastError();
-    }
-    const dim3 grid(gridFor(n)), block(256);
-    if (allInline) {
+    const PointLaunch l(n);
+    if (!l.few && allInline) {
         if (t.topDepth == 4)
-            hipLaunchKernelGGL((query_true_gradient_top_kernel<4>), grid, block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
+            hipLaunchKernelGGL((query_true_gradient_top_kernel<4>), l.grid, l.block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
         else
-            hipLaunchKernelGGL((query_true_gradient_top_kernel<0>), grid, block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
+            hipLaunchKernelGGL((query_true_gradient_top_kernel<0>), l.grid, l.block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
         return hipGetLastError();
     }
-    if (t.maxDegree <= 2)
-        hipLaunchKernelGGL((query_true_gradient_kernel<2>), grid, block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
-    else if (t.maxDegree <= 3)
-        hipLaunchKernelGGL((query_true_gradient_kernel<3>), grid, block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
-    else if (t.maxDegree <= 5)
-        hipLaunchKernelGGL((query_true_gradient_kernel<5>), grid, block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
-    else
-        hipLaunchKernelGGL((query_true_gradient_kernel<12>), grid, block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
+    forMaxDegree<2, 3, 5, 12>(t.maxDegree, [&](auto P) {
+        constexpr int MAXP = decltype(P)::value;
+        if (l.few)
+            hipLaunchKernelGGL((query_true_gradient_few_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, dOut, dGrad);
+        else
+            hipLaunchKernelGGL((query_true_gradient_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dXyz, n, flags, dOut, dGrad);
+    });
     return hipGetLastError();
 }
 

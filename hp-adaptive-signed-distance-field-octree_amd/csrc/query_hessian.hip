@@ -89,27 +89,14 @@ hipError_t launchQueryHessian(hipStream_t stream, const TreeDev& t, const Device
                               double* dOut, double* dGrad, double* dHess, double* dCurv) {
     if (n == 0) return hipSuccess;
     const HessianOut o{dOut, dGrad, dHess, dCurv};
-    if (n <= kQueryFewPoints) {
-        const dim3 fgrid((unsigned)((n + 63) / 64)), fblock(64);
-        if (t.maxDegree <= 2)
-            hipLaunchKernelGGL((query_hessian_few_kernel<2>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, o);
-        else if (t.maxDegree <= 3)
-            hipLaunchKernelGGL((query_hessian_few_kernel<3>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, o);
-        else if (t.maxDegree <= 5)
-            hipLaunchKernelGGL((query_hessian_few_kernel<5>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, o);
+    const PointLaunch l(n);
+    forMaxDegree<2, 3, 5, 12>(t.maxDegree, [&](auto P) {
+        constexpr int MAXP = decltype(P)::value;
+        if (l.few)
+            hipLaunchKernelGGL((query_hessian_few_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, o);
         else
-            hipLaunchKernelGGL((query_hessian_few_kernel<12>), fgrid, fblock, 0, stream, t, dTables, dXyz, (uint32_t)n, flags, o);
-        return hipGetLastError();
-    }
-    const dim3 grid(gridFor(n)), block(256);
-    if (t.maxDegree <= 2)
-        hipLaunchKernelGGL((query_hessian_kernel<2>), grid, block, 0, stream, t, dTables, dXyz, n, flags, o);
-    else if (t.maxDegree <= 3)
-        hipLaunchKernelGGL((query_hessian_kernel<3>), grid, block, 0, stream, t, dTables, dXyz, n, flags, o);
-    else if (t.maxDegree <= 5)
-        hipLaunchKernelGGL((query_hessian_kernel<5>), grid, block, 0, stream, t, dTables, dXyz, n, flags, o);
-    else
-        hipLaunchKernelGGL((query_hessian_kernel<12>), grid, block, 0, stream, t, dTables, dXyz, n, flags, o);
+            hipLaunchKernelGGL((query_hessian_kernel<MAXP>), l.grid, l.block, 0, stream, t, dTables, dXyz, n, flags, o);
+    });
     return hipGetLastError();
 }
 

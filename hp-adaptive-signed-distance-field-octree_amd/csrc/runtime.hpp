@@ -219,23 +219,20 @@ constexpr size_t kHostMeshPoints = 2;       // mesh signed distance (hpsdf_field
 double hostQueryPoint(const hpsdf_tree& t, const double* xyz);
 void hostQueryPointWithGradient(const hpsdf_tree& t, const double* xyz, double* out, double* grad, int leftAssoc);
 bool hostQueryRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, double* tOut);
-// QueryGradient of one point on the calling thread (host_query.cpp; the arithmetic is leaf_gradient.hpp's): *out (may be null) and
-// grad[0..2]; outside the root DBL_MAX and three quiet NaNs
-void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad);
-// QueryHessian of one point on the calling thread (host_query.cpp; the arithmetic is leaf_hessian.hpp's): every output may be null
-void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad, double* hess,
-                           double* curv);
+// The point and ray calls (QueryGradient, QueryHessian, ProjectToSurface, CastRays; host_query.cpp): n rows on the calling thread, the
+// kernels' rows bit for bit, for a *_host call of a few rows and for the device-free *_block entries.  The output pointers are the
+// call's own: those it documents as optional may be null.  The *ArgumentError routines are the argument checks that the _device, _host and
+// _block entries of a call share (0: fine; otherwise the status, with the message set).
+struct CastArgs;  // ray_cast.hpp
+void hostTrueGradientRows(const hpsdf_tree& t, const double* xyz, size_t n, uint32_t flags, int leftAssoc, double* out, double* grad);
+void hostHessianRows(const hpsdf_tree& t, const double* xyz, size_t n, uint32_t flags, int leftAssoc, double* out, double* grad, double* hess,
+                     double* curv);
+void hostProjectRows(const hpsdf_tree& t, const double* xyz, size_t n, double iso, double tol, uint32_t maxIter, uint32_t flags, int leftAssoc,
+                     double* outXyz, double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus);  // outXyz may be xyz
+void hostCastRows(const hpsdf_tree& t, const double* origins, const double* dirs, const double* tMax, size_t n, const CastArgs& a, int leftAssoc,
+                  uint8_t* outStatus, double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells);
 int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const double* hess, const double* curv);
-// ProjectToSurface of one point on the calling thread (host_query.cpp): the kernels' rows bit for bit; every output but outXyz may be
-// null, outXyz may be xyz.  projectArgumentError: the argument checks the three hpsdf_project_* entries share (sets the message)
-void hostProjectPoint(const hpsdf_tree& t, const double* xyz, double iso, double tol, uint32_t maxIter, bool unit, int leftAssoc, double* outXyz,
-                      double* outVal, double* outGrad, uint8_t* outIters, uint8_t* outStatus);
 int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter);
-// CastRays of one ray on the calling thread (host_query.cpp; the statements are ray_cast.hpp's): the kernels' rows bit for bit; every
-// output but outStatus may be null.  castArgumentError: the argument checks the three hpsdf_cast_rays_* entries share (sets the message)
-struct CastArgs;
-void hostCastRay(const hpsdf_tree& t, const double* origin, const double* dir, double tMax, const CastArgs& a, int leftAssoc, uint8_t* outStatus,
-                 double* outT, double* outXyz, double* outVal, double* outGrad, uint16_t* outEvals, uint16_t* outCells);
 int castArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter, uint32_t maxCells, size_t n, const void* origins, const void* dirs,
                       const void* tMax, const void* outStatus);
 

@@ -33,6 +33,7 @@
 
 #include "block.hpp"
 #include "device_types.hpp"
+#include "launch.hpp"
 #include "leaf_eval.hpp"
 #include "runtime.hpp"
 #include "surface_table.hpp"
@@ -613,12 +614,9 @@ template <bool EMIT>
 hipError_t launchBlocks(hipStream_t s, const TreeDev& td, const DeviceTables* T, const SparseLattice& g, double iso, const uint64_t* dActive,
                         uint64_t nActive, const BlockOut& o) {
     const dim3 grid((unsigned)(nActive < (1u << 20) ? nActive : (1u << 20))), block(kThreads);
-    if (td.maxDegree <= 3)
-        hipLaunchKernelGGL((sparse_block_kernel<3, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
-    else if (td.maxDegree <= 5)
-        hipLaunchKernelGGL((sparse_block_kernel<5, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
-    else
-        hipLaunchKernelGGL((sparse_block_kernel<12, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
+    forMaxDegree<3, 5, 12>(td.maxDegree, [&](auto P) {
+        hipLaunchKernelGGL((sparse_block_kernel<decltype(P)::value, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
+    });
     return hipGetLastError();
 }
 
