@@ -649,7 +649,9 @@ typedef struct hpsdf_job { /* one popped heap entry (BuildThreadPool::Input, Bui
 typedef struct hpsdf_build_stats { /* 112 bytes since ABI 3, frozen (see HPSDF_ABI_VERSION) */
     uint64_t rounds, jobs, p_refines, h_refines, dropped, fits, samples;
     uint64_t n_nodes, n_leaves, n_coeffs;
-    double total_error;
+    double total_error;  /* the reference's running float64 total (Octree.cpp:212, :257, :272, :276) as its stop rule reads it, not the sum
+                            of the leaves' errors: round 0's 4096 additions to 409 600 leave a drift of 1e-9..1e-8 (bound 9e-8), so below
+                            about 1e-8 it can end under the target, or negative, with the true sum far above it */
     uint64_t fit_mode;   /* HPSDF_FIT_* the build ran in */
     uint64_t split_fits; /* from-scratch fits whose rows below the top degree came from the sum-factorised / matrix-core kernel (HPSDF_FIT_SPLIT,
                             degree >= split_min_degree); 0: every coefficient is the bit-exact kernel's */
