@@ -736,20 +736,10 @@ class DeviceTree:
     def extract_surface(self, lo, hi, n, iso=0.0, values=False):
         """Marching cubes over the lattice of n[a] cubes per axis on [lo, hi] (include/hpsdf.h, hpsdf_extract_surface) ->
         (verts f64 [V,3], tris u64 [T,3]), plus the lattice values f64 [n2+1, n1+1, n0+1] when values is true."""
-        lo3 = (C.c_double * 3)(*[float(x) for x in lo])
-        hi3 = (C.c_double * 3)(*[float(x) for x in hi])
-        n3 = (C.c_uint32 * 3)(*[int(x) for x in n])
+        lo3, hi3, n3 = _lattice_args(lo, hi, n)
         vals = np.empty((int(n[2]) + 1, int(n[1]) + 1, int(n[0]) + 1)) if values else None
-        v, t = C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)()
-        nv, nt = C.c_uint64(), C.c_uint64()
-        check(lib().hpsdf_extract_surface(self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), C.byref(v), C.byref(nv), C.byref(t),
-                                          C.byref(nt), vals.ctypes.data_as(C.c_void_p) if values else None))
-        verts, tris = np.zeros((0, 3)), np.zeros((0, 3), np.uint64)
-        if nt.value:
-            verts = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
-            tris = np.ctypeslib.as_array(t, shape=(nt.value, 3)).copy()
-        lib()._libc.free(C.cast(v, C.c_void_p))
-        lib()._libc.free(C.cast(t, C.c_void_p))
+        verts, tris = _take_mesh(lambda *out: lib().hpsdf_extract_surface(
+            self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), *out, vals.ctypes.data_as(C.c_void_p) if values else None))
         return (verts, tris, vals) if values else (verts, tris)
 
     def extract_surface_sparse(self, lo, hi, n, iso=0.0, stats=False):
@@ -758,16 +748,8 @@ class DeviceTree:
         tris u64 [T,3]), plus the call's statistics as a dict when stats is true."""
         lo3, hi3, n3 = _lattice_args(lo, hi, n)
         st = SurfaceSparseStats()
-        v, t = C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)()
-        nv, nt = C.c_uint64(), C.c_uint64()
-        check(lib().hpsdf_extract_surface_sparse(self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), C.byref(v), C.byref(nv), C.byref(t),
-                                                 C.byref(nt), C.byref(st)))
-        verts, tris = np.zeros((0, 3)), np.zeros((0, 3), np.uint64)
-        if nt.value:
-            verts = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
-            tris = np.ctypeslib.as_array(t, shape=(nt.value, 3)).copy()
-        lib()._libc.free(C.cast(v, C.c_void_p))
-        lib()._libc.free(C.cast(t, C.c_void_p))
+        verts, tris = _take_mesh(lambda *out: lib().hpsdf_extract_surface_sparse(
+            self.ctx.handle, self.handle, lo3, hi3, n3, float(iso), *out, C.byref(st)))
         if not stats:
             return verts, tris
         return verts, tris, {k: getattr(st, k) for k, _ in SurfaceSparseStats._fields_ if k != "reserved"}
@@ -1338,6 +1320,20 @@ def query_gradient_block(block, pts, unit=False):
 
 def _lattice_args(lo, hi, n):
     return ((C.c_double * 3)(*[float(x) for x in lo]), (C.c_double * 3)(*[float(x) for x in hi]), (C.c_uint32 * 3)(*[int(x) for x in n]))
+
+
+def _take_mesh(call):
+    """call(verts, n_verts, tris, n_tris): an extraction's malloc'd result -> (verts f64 [V,3], tris u64 [T,3]), the C arrays freed."""
+    v, t = C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)()
+    nv, nt = C.c_uint64(), C.c_uint64()
+    check(call(C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
+    verts, tris = np.zeros((0, 3)), np.zeros((0, 3), np.uint64)
+    if nt.value:
+        verts = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
+        tris = np.ctypeslib.as_array(t, shape=(nt.value, 3)).copy()
+    lib()._libc.free(C.cast(v, C.c_void_p))
+    lib()._libc.free(C.cast(t, C.c_void_p))
+    return verts, tris
 
 
 def surface_block_count(n):

@@ -1,0 +1,277 @@
+// What hpsdf_extract_surface (surface.hip) and hpsdf_extract_surface_sparse (surface_sparse.hip) share.  The sparse call promises the
+// dense call's mesh bit for bit, so everything both must agree on is written here once: the packed case table and its decode, the
+// vertex arithmetic, the wave helpers, the check of the lattice arguments, and the host scaffolding of a call (events, device memory,
+// rocPRIM's two-call pattern, the malloc'd outputs).  Included by those two units only; each gets its own __constant__ copies.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "host_call.hpp"
+#include "runtime.hpp"
+#include "surface_table.hpp"
+#include "hpsdf.h"
+
+namespace hpsdf {
+
+namespace {
+
+// ---- case table ------------------------------------------------------------------------------------------------------------------
+
+struct PackedCases {
+    uint64_t v[256];
+};
+constexpr PackedCases packCases() {
+    const SurfaceTable T = makeSurfaceTable();
+    PackedCases p{};
+    for (int i = 0; i < 256; ++i) p.v[i] = T.packed[i];
+    return p;
+}
+constexpr bool tableFits() {  // 3 bits of count and 12 bits a triangle in 64
+    const SurfaceTable T = makeSurfaceTable();
+    for (int i = 0; i < 256; ++i)
+        if (T.count[i] > kSurfaceMaxTris) return false;
+    return T.faceFreeFans;
+}
+static_assert(tableFits(), "a case of the face-local rule needs more than kSurfaceMaxTris triangles, or a loop has no apex whose fan stays out of the faces");
+
+__constant__ PackedCases kSurfaceCases = packCases();
+
+// cube-local edge -> its lower corner and axis (surface_table.hpp's numbering)
+__constant__ uint8_t kEdgeCorner[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
+__constant__ uint8_t kEdgeAxis[12] = {0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2};
+
+constexpr unsigned kSurfThreads = 256;  // the workgroup of every kernel of both units
+
+// the packed table into LDS (the caller synchronises)
+__device__ __forceinline__ void stageCases(uint64_t* sCase) {
+    for (unsigned c = threadIdx.x; c < 256u; c += kSurfThreads) sCase[c] = kSurfaceCases.v[c];
+}
+
+// A packed case (surface_table.hpp): bits 0-2 the triangle count, then the triangles' cube-local edges.  The edge of vertex m of
+// triangle tr, as its lower corner (dx + 2 dy + 4 dz) and its axis:
+__device__ __forceinline__ uint32_t caseEdge(uint64_t pk, uint32_t tr, int m) { return (uint32_t)(pk >> (3 + 12 * tr + 4 * m)) & 15u; }
+__device__ __forceinline__ uint8_t caseCorner(uint64_t pk, uint32_t tr, int m) { return kEdgeCorner[caseEdge(pk, tr, m)]; }
+__device__ __forceinline__ uint8_t caseAxis(uint64_t pk, uint32_t tr, int m) { return kEdgeAxis[caseEdge(pk, tr, m)]; }
+
+// ---- vertex arithmetic (include/hpsdf.h) -------------------------------------------------------------------------------------------
+
+// The vertex on the edge from lattice point idx = (i, j, k) along axis a, whose ends hold va and vb.  Both calls' vertices are these
+// statements in this order; no multiply-add is fused (the build's -ffp-contract=off).
+__host__ __device__ __forceinline__ void edgeVertex(const double* lo, const double* h, const uint32_t (&idx)[3], uint32_t a, double va, double vb,
+                                                    double iso, double (&p)[3]) {
+    const double t = (iso - va) / (vb - va);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) p[d] = lo[d] + (double)idx[d] * h[d];
+    const double xb = lo[a] + (double)(idx[a] + 1u) * h[a];
+    p[a] = p[a] + t * (xb - p[a]);
+}
+
+// ---- wave helpers ------------------------------------------------------------------------------------------------------------------
+
+// set bits of a ballot mask in the lanes below this one: the rank of this lane's bit among the wave's
+__device__ __forceinline__ uint32_t rankBelow(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// sum of n over the wave's lanes below this one: the wave's inclusive sum less the lane's own
+__device__ __forceinline__ uint32_t sumBelow(uint32_t n, uint32_t lane) {
+    uint32_t incl = n;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o, 64);
+        if (lane >= (uint32_t)o) incl += y;
+    }
+    return incl - n;
+}
+
+inline unsigned gridOf(uint64_t threads, unsigned cap = 65536) {
+    const uint64_t b = (threads + kSurfThreads - 1) / kSurfThreads;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// ---- lattice arguments -------------------------------------------------------------------------------------------------------------
+
+struct LatticeLimits {
+    int axisLog2;    // n[a] <= 2^axisLog2 (32: no limit of its own)
+    int pointsLog2;  // lattice points <= 2^pointsLog2
+};
+constexpr LatticeLimits kDenseLimits = {32, 30}, kSparseLimits = {20, 40};
+
+struct CheckedLattice {
+    double lo[3], h[3];
+    uint32_t n[3];
+    uint64_t nPts, nCubes;
+};
+
+inline bool inRoot(const double* rc, const double* ris, int a, double x) {  // Query's f32 containment test (leaf_eval.hpp) on one coordinate
+    const float f = (float)((x - rc[a]) * ris[a]);
+    return f >= -0.5f && f <= 0.5f;
+}
+
+// The lattice arguments of an entry point named `what`, against a tree's root map (rootCentre, rootInvSizes).  Order of the checks:
+// iso; per axis finite, lo < hi, n; the number of points; per axis the containment test.
+inline int checkLattice(const char* what, const LatticeLimits& lim, const double* rc, const double* ris, const double* lo, const double* hi,
+                        const uint32_t* n, double iso, CheckedLattice* out) {
+    static const char* kAxis[3] = {"x", "y", "z"};
+    const auto bad = [what](const std::string& msg) { return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(what) + ": " + msg); };
+    const auto badAxis = [&](int a, const std::string& msg) { return bad(std::string("axis ") + kAxis[a] + ": " + msg); };
+    if (!std::isfinite(iso)) return bad("iso must be finite");
+    CheckedLattice g{};
+    g.nPts = 1, g.nCubes = 1;
+    bool tooMany = false;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return badAxis(a, "lo and hi must be finite");
+        if (!(lo[a] < hi[a])) return badAxis(a, "lo must be below hi");
+        if (n[a] < 1) return badAxis(a, "n must be at least 1");
+        if (n[a] > (1ull << lim.axisLog2)) return badAxis(a, "n must be at most 2^" + std::to_string(lim.axisLog2));
+        if (!tooMany) {  // (a product within the limit times a factor below 2^33 stays below 2^64)
+            g.nPts *= (uint64_t)n[a] + 1u;
+            g.nCubes *= n[a];
+            tooMany = g.nPts > (1ull << lim.pointsLog2);
+        }
+        g.lo[a] = lo[a];
+        g.h[a] = (hi[a] - lo[a]) / (double)n[a];
+        g.n[a] = n[a];
+    }
+    if (tooMany) return bad("more than 2^" + std::to_string(lim.pointsLog2) + " lattice points");
+    for (int a = 0; a < 3; ++a) {
+        // the containment test is monotone along an axis: the two extreme lattice points decide for all of them
+        const double last = g.lo[a] + (double)n[a] * g.h[a];
+        if (!inRoot(rc, ris, a, g.lo[a]) || !inRoot(rc, ris, a, last))
+            return badAxis(a, "the box leaves the tree's root (Query would return DBL_MAX there)");
+    }
+    *out = g;
+    return HPSDF_OK;
+}
+
+// ---- host scaffolding of a call ----------------------------------------------------------------------------------------------------
+
+// N events on the call's stream; a failure to create or record one only zeroes the times
+template <int N>
+struct Events {
+    hipEvent_t e[N] = {};
+    bool ok = true;
+    Events() {
+        for (auto& x : e)
+            if (hipEventCreate(&x) != hipSuccess) x = nullptr, ok = false;
+        if (!ok) (void)hipGetLastError();
+    }
+    ~Events() {
+        for (auto& x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    void mark(int i, hipStream_t s) {
+        if (ok && hipEventRecord(e[i], s) != hipSuccess) ok = false;
+    }
+    double ms(int a, int b) const {
+        float r = 0.0f;
+        return ok && hipEventElapsedTime(&r, e[a], e[b]) == hipSuccess ? (double)r : 0.0;
+    }
+};
+
+// The device memory of one call of the entry point `what`: what is live, the most that was, and everything freed when the call ends.
+// The dense call takes one allocation and carves it; the sparse call takes and releases its arrays by name to keep the peak low.
+struct DevPool {
+    const char* what;
+    std::vector<std::pair<void*, size_t>> live;
+    size_t cur = 0, peak = 0;
+    explicit DevPool(const char* w) : what(w) {}
+    DevPool(const DevPool&) = delete;
+    // HPSDF_OK, or the failure's code with its message set: running out of device memory names the array
+    template <typename T>
+    int alloc(T*& p, size_t bytes, const char* name) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes < 256 ? 256 : bytes);
+        p = e == hipSuccess ? (T*)q : nullptr;
+        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
+            (void)hipGetLastError();
+            return fail(HPSDF_ERR_OUT_OF_MEMORY, std::string(what) + ": out of device memory (" + name + ")");
+        }
+        if (e != hipSuccess) return hipFail(e, "hipMalloc");
+        live.emplace_back(q, bytes);
+        cur += bytes;
+        peak = cur > peak ? cur : peak;
+        return HPSDF_OK;
+    }
+    template <typename T>
+    void release(T*& p) {  // (the stream must have passed the array's last use)
+        for (auto& x : live)
+            if (x.first == (void*)p && p != nullptr) {
+                (void)hipFree(x.first);
+                cur -= x.second;
+                x = live.back();
+                live.pop_back();
+                break;
+            }
+        p = nullptr;
+    }
+    ~DevPool() {
+        for (auto& x : live) (void)hipFree(x.first);
+    }
+};
+
+#define SURF_ALLOC(pool, ptr, bytes, name)                                     \
+    do {                                                                       \
+        if (const int rc_ = (pool).alloc((ptr), (bytes), (name))) return rc_; \
+    } while (0)
+
+// the status of a rocPRIM step behind a lambda: a failure names the primitive (`prim`, e.g. "rocprim::reduce"), not the lambda
+inline int primStatus(hipError_t e, const char* prim) { return e == hipSuccess ? HPSDF_OK : hipFail(e, prim); }
+
+// rocPRIM's two-call pattern: call(nullptr, bytes) asks for the size of the temporary storage, which then comes from the pool under
+// `name`, and call(tmp, bytes) runs.  tmp stays the caller's to release (or to run the same call on other arrays first).
+template <typename Call>
+int withTemp(DevPool& pool, const char* prim, const char* name, void*& tmp, size_t& bytes, Call&& call) {
+    bytes = 0;
+    if (const int rc = primStatus(call(nullptr, bytes), prim)) return rc;
+    SURF_ALLOC(pool, tmp, bytes, name);
+    if (const int rc = primStatus(call(tmp, bytes), prim)) return rc;
+    return HPSDF_OK;
+}
+
+// the scan of both calls' counts (uint32 counts -> uint64 exclusive prefixes) in withTemp's form
+constexpr const char* kPrefixScan = "rocprim::exclusive_scan";
+inline auto prefixScan(const uint32_t* in, uint64_t* out, uint64_t count, hipStream_t s) {
+    return [=](void* tmp, size_t& bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, (size_t)count, rocprim::plus<uint64_t>(), s);
+    };
+}
+
+struct HostOut {  // a malloc'd output, released unless handed to the caller
+    void* p = nullptr;
+    ~HostOut() { std::free(p); }
+};
+
+// The mesh on its way to the caller: host arrays for V vertices and T triangles, their download, and the handing over
+struct MeshOut {
+    HostOut v, t;
+    uint64_t V = 0, T = 0;
+    int alloc(const char* what, uint64_t nVerts, uint64_t nTris) {
+        V = nVerts, T = nTris;
+        v.p = std::malloc(V * 3 * sizeof(double));
+        t.p = std::malloc(T * 3 * sizeof(uint64_t));
+        return v.p && t.p ? HPSDF_OK : fail(HPSDF_ERR_OUT_OF_MEMORY, std::string(what) + ": host allocation failed");
+    }
+    int download(const double* dVerts, const uint64_t* dTris, hipStream_t s) {
+        HPSDF_HIP(hipMemcpyAsync(v.p, dVerts, V * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HPSDF_HIP(hipMemcpyAsync(t.p, dTris, T * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        return HPSDF_OK;
+    }
+    void handOver(double** verts, uint64_t* nVerts, uint64_t** tris, uint64_t* nTris) {
+        *verts = (double*)v.p, *tris = (uint64_t*)t.p;
+        v.p = nullptr, t.p = nullptr;
+        *nVerts = V, *nTris = T;
+    }
+};
+
+}  // namespace
+
+}  // namespace hpsdf

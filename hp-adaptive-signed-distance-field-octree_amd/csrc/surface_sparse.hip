@@ -1,5 +1,6 @@
 // hpsdf_extract_surface_sparse: hpsdf_extract_surface's mesh, bit for bit, evaluated only in the blocks of 8^3 cubes the tree cannot
-// rule out (include/hpsdf.h states the blocks, the classes, the bound and the derivation of its slack).
+// rule out (include/hpsdf.h states the blocks, the classes, the bound and the derivation of its slack).  What must equal the dense
+// call's -- case table, vertex arithmetic, wave helpers, argument checks -- is surface_common.hpp's, included by both.
 //
 //   1. sparse_depth_kernel / sparse_consts_kernel: per leaf G_x, G_y, G_z, S (leafBound) -- the depth of a node is not in the 8-byte
 //      mirror, one workgroup hands it down level by level;
@@ -16,17 +17,13 @@
 // No atomics on anything that reaches the output (one counter of visited leaves for the statistics).
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <string>
-#include <utility>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -35,10 +32,8 @@
 #include "device_types.hpp"
 #include "launch.hpp"
 #include "leaf_eval.hpp"
-#include "runtime.hpp"
-#include "surface_table.hpp"
+#include "surface_common.hpp"
 #include "tables.hpp"
-#include "hpsdf.h"
 
 namespace hpsdf {
 
@@ -48,9 +43,8 @@ constexpr uint32_t kB = HPSDF_SURFACE_BLOCK;  // cubes per axis of a block
 constexpr uint32_t kP = kB + 1;               // points per axis of its closed range
 constexpr uint32_t kBlockPts = kP * kP * kP;  // 729
 constexpr uint32_t kBlockCubes = kB * kB * kB;
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kEdgeRounds = (3 * kBlockPts + kThreads - 1) / kThreads;  // 9
-constexpr uint32_t kCubeRounds = kBlockCubes / kThreads;                     // 2
+constexpr uint32_t kEdgeRounds = (3 * kBlockPts + kSurfThreads - 1) / kSurfThreads;  // 9
+constexpr uint32_t kCubeRounds = kBlockCubes / kSurfThreads;                     // 2
 constexpr int kLevels = HPSDF_TREE_MAX_DEPTH + 2;
 constexpr double kClip = 1.0 + 1.0 / 16384.0;  // 1 + E, E = 2^-14 (include/hpsdf.h)
 
@@ -225,10 +219,10 @@ __global__ __launch_bounds__(1024) void sparse_depth_kernel(const NodeRec* __res
     }
 }
 
-__global__ __launch_bounds__(kThreads) void sparse_consts_kernel(const NodeRec* __restrict__ nodes, const double* __restrict__ coeffs,
+__global__ __launch_bounds__(kSurfThreads) void sparse_consts_kernel(const NodeRec* __restrict__ nodes, const double* __restrict__ coeffs,
                                                                  const uint8_t* __restrict__ depth, uint32_t nNodes,
                                                                  const DeviceTables* __restrict__ T, double* __restrict__ consts) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t i = blockIdx.x * kSurfThreads + threadIdx.x;
     if (i >= nNodes) return;
     double out[4] = {0.0, 0.0, 0.0, 0.0};
     const NodeRec rec = nodes[i];
@@ -237,7 +231,7 @@ __global__ __launch_bounds__(kThreads) void sparse_consts_kernel(const NodeRec* 
     for (int k = 0; k < 4; ++k) consts[4 * (size_t)i + k] = out[k];
 }
 
-__global__ __launch_bounds__(kThreads) void sparse_classify_kernel(ClsTree t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
+__global__ __launch_bounds__(kSurfThreads) void sparse_classify_kernel(ClsTree t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
                                                                    uint64_t firstBlock, uint64_t count, uint8_t* __restrict__ out,
                                                                    unsigned long long* __restrict__ visitedTotal) {
     __shared__ double sNl[13 * 11];
@@ -246,8 +240,8 @@ __global__ __launch_bounds__(kThreads) void sparse_classify_kernel(ClsTree t, co
     __syncthreads();
     const DevEval eval{sNl, sRec};
     unsigned long long mine = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < count; i += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kSurfThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSurfThreads + threadIdx.x; i < count; i += stride) {
         uint32_t visited;
         out[i] = classifyBlock(t, g, iso, firstBlock + i, eval, visited);
         mine += visited;
@@ -260,20 +254,6 @@ __global__ __launch_bounds__(kThreads) void sparse_classify_kernel(ClsTree t, co
 }
 
 // ---- the active blocks ---------------------------------------------------------------------------------------------------------
-
-struct PackedCases {
-    uint64_t v[256];
-};
-constexpr PackedCases packCases() {
-    const SurfaceTable T = makeSurfaceTable();
-    PackedCases p{};
-    for (int i = 0; i < 256; ++i) p.v[i] = T.packed[i];
-    return p;
-}
-__constant__ PackedCases kSparseCases = packCases();
-// cube-local edge -> its lower corner and axis (surface_table.hpp's numbering)
-__constant__ uint8_t kSparseEdgeCorner[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
-__constant__ uint8_t kSparseEdgeAxis[12] = {0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2};
 
 struct BlockOut {
     uint32_t* vcount;  // COUNT: per active block
@@ -288,12 +268,8 @@ struct BlockOut {
     uint64_t* tedge;
 };
 
-__device__ __forceinline__ uint32_t rankBelow(uint64_t mask) {  // set bits of the ballot in the lanes below this one
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 template <int MAXP, bool EMIT>
-__global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
+__global__ __launch_bounds__(kSurfThreads) void sparse_block_kernel(TreeDev t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
                                                                 const uint64_t* __restrict__ active, uint64_t nActive, BlockOut o) {
     __shared__ double sNl[13 * 11];
     __shared__ double sRec[26];
@@ -302,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
     __shared__ uint8_t sIn[kBlockPts + 7];
     __shared__ uint32_t sVW[4], sTW[kCubeRounds][4];
     stageQueryTables(T, sNl, sRec);
-    for (uint32_t c = threadIdx.x; c < 256u; c += kThreads) sCase[c] = kSparseCases.v[c];
+    stageCases(sCase);
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     for (uint64_t ab = blockIdx.x; ab < nActive; ab += gridDim.x) {
         __syncthreads();  // the tables are staged; the previous block's LDS is no longer read
@@ -315,7 +291,7 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
             cnt[a] = g.n[a] - base[a] < kB ? g.n[a] - base[a] : kB;  // cubes of the block on this axis
             own[a] = cnt[a] + (bi[a] + 1u == g.nb[a] ? 1u : 0u);     // points whose edges it owns: the last block also owns the boundary layer
         }
-        for (uint32_t p = tid; p < kBlockPts; p += kThreads) {
+        for (uint32_t p = tid; p < kBlockPts; p += kSurfThreads) {
             const uint32_t lx = p % kP, ly = (p / kP) % kP, lz = p / (kP * kP);
             double v = 0.0;
             if (lx <= cnt[0] && ly <= cnt[1] && lz <= cnt[2]) {
@@ -348,13 +324,13 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
         uint32_t vw = 0;
         for (uint32_t r = 0; r < kEdgeRounds; ++r) {
             uint32_t p, ax;
-            vw += (uint32_t)__popcll(__ballot(crosses(r * kThreads + tid, p, ax)));
+            vw += (uint32_t)__popcll(__ballot(crosses(r * kSurfThreads + tid, p, ax)));
         }
         uint32_t tn[kCubeRounds];
         uint64_t pk[kCubeRounds];
         uint32_t cl[kCubeRounds][3];
         for (uint32_t r = 0; r < kCubeRounds; ++r) {
-            pk[r] = cubeCase(r * kThreads + tid, cl[r]);
+            pk[r] = cubeCase(r * kSurfThreads + tid, cl[r]);
             tn[r] = (uint32_t)(pk[r] & 7u);
             uint32_t sum = tn[r];
 #pragma unroll
@@ -375,21 +351,16 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
             for (uint32_t w = 0; w < wave; ++w) vpos += sVW[w];
             for (uint32_t r = 0; r < kEdgeRounds; ++r) {
                 uint32_t p, ax;
-                const bool c = crosses(r * kThreads + tid, p, ax);
+                const bool c = crosses(r * kSurfThreads + tid, p, ax);
                 const uint64_t m = __ballot(c);
                 if (c) {
                     const uint64_t at = vpos + rankBelow(m);
                     const uint32_t l[3] = {p % kP, (p / kP) % kP, p / (kP * kP)};
                     const uint32_t idx[3] = {base[0] + l[0], base[1] + l[1], base[2] + l[2]};
                     const uint32_t s = ax == 0 ? 1u : (ax == 1 ? kP : kP * kP);
-                    // hpsdf_extract_surface's vertex (surface.hip, surf_vertex_kernel): the same statements
                     const double va = sV[p], vb = sV[p + s];
-                    const double tt = (iso - va) / (vb - va);
                     double q[3];
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) q[d] = g.lo[d] + (double)idx[d] * g.h[d];
-                    const double xb = g.lo[ax] + (double)(idx[ax] + 1u) * g.h[ax];
-                    q[ax] = q[ax] + tt * (xb - q[ax]);
+                    edgeVertex(g.lo, g.h, idx, ax, va, vb, iso, q);
                     o.vkey[at] = 3u * (idx[0] + g.np[0] * (idx[1] + g.np[1] * (uint64_t)idx[2])) + ax;
                     o.vidx[at] = at;
                     o.vxyz[3 * at] = q[0], o.vxyz[3 * at + 1] = q[1], o.vxyz[3 * at + 2] = q[2];
@@ -398,13 +369,7 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
             }
             uint64_t tpos = o.tprefix[ab];
             for (uint32_t r = 0; r < kCubeRounds; ++r) {
-                uint32_t incl = tn[r];  // inclusive sum over the wave's lanes
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t y = __shfl_up(incl, off, 64);
-                    if (lane >= (uint32_t)off) incl += y;
-                }
-                uint64_t at = tpos + (incl - tn[r]);
+                uint64_t at = tpos + sumBelow(tn[r], lane);
                 for (uint32_t w = 0; w < wave; ++w) at += sTW[r][w];
                 if (tn[r] != 0) {
                     const uint32_t i = base[0] + cl[r][0], j = base[1] + cl[r][1], k = base[2] + cl[r][2];
@@ -414,10 +379,9 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
                         o.tidx[at + tr] = at + tr;
 #pragma unroll
                         for (int m = 0; m < 3; ++m) {
-                            const uint32_t le = (uint32_t)(pk[r] >> (3 + 12 * tr + 4 * m)) & 15u;
-                            const uint32_t cr = kSparseEdgeCorner[le];
+                            const uint32_t cr = caseCorner(pk[r], tr, m);
                             const uint64_t L = (i + (cr & 1u)) + g.np[0] * ((j + ((cr >> 1) & 1u)) + g.np[1] * (uint64_t)(k + (cr >> 2)));
-                            o.tedge[3 * (at + tr) + m] = 3u * L + kSparseEdgeAxis[le];
+                            o.tedge[3 * (at + tr) + m] = 3u * L + caseAxis(pk[r], tr, m);
                         }
                     }
                 }
@@ -427,20 +391,20 @@ __global__ __launch_bounds__(kThreads) void sparse_block_kernel(TreeDev t, const
     }
 }
 
-__global__ __launch_bounds__(kThreads) void sparse_gather_kernel(const uint64_t* __restrict__ order, const double* __restrict__ xyz, uint64_t n,
+__global__ __launch_bounds__(kSurfThreads) void sparse_gather_kernel(const uint64_t* __restrict__ order, const double* __restrict__ xyz, uint64_t n,
                                                                  double* __restrict__ out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kSurfThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSurfThreads + threadIdx.x; i < n; i += stride) {
         const uint64_t s = order[i];
         out[3 * i] = xyz[3 * s], out[3 * i + 1] = xyz[3 * s + 1], out[3 * i + 2] = xyz[3 * s + 2];
     }
 }
 
 // triangle i of the sorted order: its three edge ids -> their ranks among the sorted vertex keys (every one of them is there)
-__global__ __launch_bounds__(kThreads) void sparse_renumber_kernel(const uint64_t* __restrict__ order, const uint64_t* __restrict__ tedge, uint64_t nTris,
+__global__ __launch_bounds__(kSurfThreads) void sparse_renumber_kernel(const uint64_t* __restrict__ order, const uint64_t* __restrict__ tedge, uint64_t nTris,
                                                                    const uint64_t* __restrict__ vkeys, uint64_t nVerts, uint64_t* __restrict__ out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < nTris; i += stride) {
+    const uint64_t stride = (uint64_t)gridDim.x * kSurfThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kSurfThreads + threadIdx.x; i < nTris; i += stride) {
         const uint64_t s = order[i];
         for (int m = 0; m < 3; ++m) {
             const uint64_t e = tedge[3 * s + m];
@@ -466,121 +430,23 @@ struct IsActiveFlag {
     __host__ __device__ bool operator()(uint8_t c) const { return c == 0; }
 };
 
-unsigned gridOf(uint64_t threads, unsigned cap = 65536) {
-    const uint64_t b = (threads + kThreads - 1) / kThreads;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-bool inRoot(const double* rc, const double* ris, int a, double x) {  // Query's f32 containment test on one coordinate
-    const float f = (float)((x - rc[a]) * ris[a]);
-    return f >= -0.5f && f <= 0.5f;
-}
-
 // the arguments of the three entry points -> the lattice; what: the entry point's name for the messages
 int makeLattice(const char* what, const double* rc, const double* ris, const double* lo, const double* hi, const uint32_t* n, double iso,
-                SparseLattice* out, uint64_t* nPtsOut, uint64_t* nCubesOut) {
-    const std::string w = std::string(what) + ": ";
-    if (!std::isfinite(iso)) return fail(HPSDF_ERR_INVALID_ARGUMENT, w + "iso must be finite");
-    static const char* kAxis[3] = {"x", "y", "z"};
+                SparseLattice* out, CheckedLattice* checked = nullptr) {
+    CheckedLattice cl{};
+    if (const int r = checkLattice(what, kSparseLimits, rc, ris, lo, hi, n, iso, &cl)) return r;
     SparseLattice g{};
-    uint64_t nPts = 1, nCubes = 1;
     g.nBlocks = 1;
     for (int a = 0; a < 3; ++a) {
-        const std::string ax = w + "axis " + kAxis[a] + ": ";
-        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo and hi must be finite");
-        if (!(lo[a] < hi[a])) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "lo must be below hi");
-        if (n[a] < 1) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "n must be at least 1");
-        if (n[a] > (1u << 20)) return fail(HPSDF_ERR_INVALID_ARGUMENT, ax + "n must be at most 2^20");
-        nPts *= (uint64_t)n[a] + 1u;  // (< 2^63: three factors below 2^21)
-        nCubes *= n[a];
-        g.lo[a] = lo[a];
-        g.h[a] = (hi[a] - lo[a]) / (double)n[a];
-        g.n[a] = n[a];
-        g.np[a] = (uint64_t)n[a] + 1u;
-        g.nb[a] = (n[a] + kB - 1) / kB;
+        g.lo[a] = cl.lo[a], g.h[a] = cl.h[a], g.n[a] = cl.n[a];
+        g.np[a] = (uint64_t)cl.n[a] + 1u;
+        g.nb[a] = (cl.n[a] + kB - 1) / kB;
         g.nBlocks *= g.nb[a];
     }
-    if (nPts > (1ull << 40)) return fail(HPSDF_ERR_INVALID_ARGUMENT, w + "more than 2^40 lattice points");
-    for (int a = 0; a < 3; ++a) {
-        // the containment test is monotone along an axis: the two extreme lattice points decide for all of them
-        const double last = g.lo[a] + (double)n[a] * g.h[a];
-        if (!inRoot(rc, ris, a, g.lo[a]) || !inRoot(rc, ris, a, last))
-            return fail(HPSDF_ERR_INVALID_ARGUMENT, w + "axis " + kAxis[a] + ": the box leaves the tree's root (Query would return DBL_MAX there)");
-    }
     *out = g;
-    if (nPtsOut) *nPtsOut = nPts;
-    if (nCubesOut) *nCubesOut = nCubes;
+    if (checked) *checked = cl;
     return HPSDF_OK;
 }
-
-// The call's device memory: what is live, the most that was, and everything freed when the call ends.
-struct DevPool {
-    std::vector<std::pair<void*, size_t>> live;
-    size_t cur = 0, peak = 0;
-    bool oom = false;
-    hipError_t alloc(void** p, size_t bytes) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc(p, bytes < 256 ? 256 : bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            oom = e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation;
-            return e;
-        }
-        live.emplace_back(*p, bytes);
-        cur += bytes;
-        peak = cur > peak ? cur : peak;
-        return hipSuccess;
-    }
-    void release(void* p) {
-        for (auto& x : live)
-            if (x.first == p && p != nullptr) {
-                (void)hipFree(p);
-                cur -= x.second;
-                x = live.back();
-                live.pop_back();
-                return;
-            }
-    }
-    ~DevPool() {
-        for (auto& x : live) (void)hipFree(x.first);
-    }
-};
-
-#define SPARSE_ALLOC(pool, ptr, bytes, name)                                                                        \
-    do {                                                                                                            \
-        const hipError_t ea_ = (pool).alloc((void**)&(ptr), (bytes));                                                \
-        if (ea_ != hipSuccess && (pool).oom)                                                                         \
-            return fail(HPSDF_ERR_OUT_OF_MEMORY, std::string(kWhat) + ": out of device memory (" + (name) + ")"); \
-        HPSDF_HIP(ea_);                                                                                             \
-    } while (0)
-
-struct Events {
-    static constexpr int kN = 10;
-    hipEvent_t e[kN] = {};
-    bool ok = true;
-    Events() {
-        for (auto& x : e)
-            if (hipEventCreate(&x) != hipSuccess) x = nullptr, ok = false;
-        if (!ok) (void)hipGetLastError();
-    }
-    ~Events() {
-        for (auto& x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    void mark(int i, hipStream_t s) {
-        if (ok && hipEventRecord(e[i], s) != hipSuccess) ok = false;
-    }
-    double ms(int a, int b) const {
-        float r = 0.0f;
-        return ok && hipEventElapsedTime(&r, e[a], e[b]) == hipSuccess ? (double)r : 0.0;
-    }
-};
-
-struct HostOut {  // malloc'd outputs, released unless handed to the caller
-    void* p = nullptr;
-    ~HostOut() { std::free(p); }
-};
 
 unsigned bitsFor(uint64_t maxKey) {  // radix passes stop at the highest bit a key can have
     unsigned b = 1;
@@ -589,23 +455,23 @@ unsigned bitsFor(uint64_t maxKey) {  // radix passes stop at the highest bit a k
 }
 
 // constants of the tree's leaves and the classes of blocks [first, first + count) into dClass; the stream is not synchronised
-int classifyOnDevice(const char* kWhat, hpsdf_ctx* ctx, const hpsdf_tree* t, DevPool& pool, const SparseLattice& g, double iso, uint64_t first,
+int classifyOnDevice(hpsdf_ctx* ctx, const hpsdf_tree* t, DevPool& pool, const SparseLattice& g, double iso, uint64_t first,
                      uint64_t count, uint8_t* dClass, unsigned long long* dVisited) {
     hipStream_t s = ctx->stream;
     const uint32_t nNodes = (uint32_t)t->nNodes;
     uint8_t* dDepth = nullptr;
     double* dConsts = nullptr;
-    SPARSE_ALLOC(pool, dDepth, (size_t)nNodes, "node depths");
-    SPARSE_ALLOC(pool, dConsts, (size_t)nNodes * 4 * sizeof(double), "leaf constants");
+    SURF_ALLOC(pool, dDepth, (size_t)nNodes, "node depths");
+    SURF_ALLOC(pool, dConsts, (size_t)nNodes * 4 * sizeof(double), "leaf constants");
     hipLaunchKernelGGL(sparse_depth_kernel, dim3(1), dim3(1024), 0, s, t->dev.nodes, nNodes, t->maxDepth, dDepth);
     HPSDF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sparse_consts_kernel, dim3(gridOf(nNodes, 1u << 24)), dim3(kThreads), 0, s, t->dev.nodes, t->dev.coeffs, dDepth, nNodes,
+    hipLaunchKernelGGL(sparse_consts_kernel, dim3(gridOf(nNodes, 1u << 24)), dim3(kSurfThreads), 0, s, t->dev.nodes, t->dev.coeffs, dDepth, nNodes,
                        ctx->dTables, dConsts);
     HPSDF_HIP(hipGetLastError());
     ClsTree ct{};
     ct.nodes = t->dev.nodes, ct.coeffs = t->dev.coeffs, ct.consts = dConsts;
     for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
-    hipLaunchKernelGGL(sparse_classify_kernel, dim3(gridOf(count)), dim3(kThreads), 0, s, ct, ctx->dTables, g, iso, first, count, dClass, dVisited);
+    hipLaunchKernelGGL(sparse_classify_kernel, dim3(gridOf(count)), dim3(kSurfThreads), 0, s, ct, ctx->dTables, g, iso, first, count, dClass, dVisited);
     HPSDF_HIP(hipGetLastError());
     return HPSDF_OK;
 }
@@ -613,7 +479,7 @@ int classifyOnDevice(const char* kWhat, hpsdf_ctx* ctx, const hpsdf_tree* t, Dev
 template <bool EMIT>
 hipError_t launchBlocks(hipStream_t s, const TreeDev& td, const DeviceTables* T, const SparseLattice& g, double iso, const uint64_t* dActive,
                         uint64_t nActive, const BlockOut& o) {
-    const dim3 grid((unsigned)(nActive < (1u << 20) ? nActive : (1u << 20))), block(kThreads);
+    const dim3 grid((unsigned)(nActive < (1u << 20) ? nActive : (1u << 20))), block(kSurfThreads);
     forMaxDegree<3, 5, 12>(td.maxDegree, [&](auto P) {
         hipLaunchKernelGGL((sparse_block_kernel<decltype(P)::value, EMIT>), grid, block, 0, s, td, T, g, iso, dActive, nActive, o);
     });
@@ -624,12 +490,12 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
                   uint64_t* nVerts, uint64_t** tris, uint64_t* nTris, hpsdf_surface_sparse_stats* stats) {
     static const char* kWhat = "hpsdf_extract_surface_sparse";
     SparseLattice g{};
-    uint64_t nPts = 0, nCubes = 0;
-    if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, &nPts, &nCubes)) return rc;
+    CheckedLattice cl{};
+    if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, &cl)) return rc;
     HPSDF_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    DevPool pool;
-    Events ev;
+    DevPool pool(kWhat);
+    Events<9> ev;
     TreeDev td = t->dev;
     td.leftAssoc = reductionLeftAssoc(ctx);
     hpsdf_surface_sparse_stats st{};
@@ -638,23 +504,23 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
     // classes
     uint8_t* dClass = nullptr;
     unsigned long long* dScalars = nullptr;  // [0] visited leaves, [1] active blocks, [2] selected count
-    SPARSE_ALLOC(pool, dClass, (size_t)g.nBlocks, "block classes");
-    SPARSE_ALLOC(pool, dScalars, 3 * sizeof(unsigned long long), "counters");
+    SURF_ALLOC(pool, dClass, (size_t)g.nBlocks, "block classes");
+    SURF_ALLOC(pool, dScalars, 3 * sizeof(unsigned long long), "counters");
     ev.mark(0, s);
     HPSDF_HIP(hipMemsetAsync(dScalars, 0, 3 * sizeof(unsigned long long), s));
-    if (const int rc = classifyOnDevice(kWhat, ctx, t, pool, g, iso, 0, g.nBlocks, dClass, dScalars)) return rc;
+    if (const int rc = classifyOnDevice(ctx, t, pool, g, iso, 0, g.nBlocks, dClass, dScalars)) return rc;
     ev.mark(1, s);
 
     // the active blocks, in block order
     using ActiveCount = rocprim::transform_iterator<const uint8_t*, IsActive, uint64_t>;
     using ActiveFlag = rocprim::transform_iterator<const uint8_t*, IsActiveFlag, bool>;
     size_t tmpBytes = 0;
-    HPSDF_HIP(rocprim::reduce(nullptr, tmpBytes, ActiveCount(dClass, IsActive()), (uint64_t*)(dScalars + 1), (uint64_t)0, (size_t)g.nBlocks,
-                              rocprim::plus<uint64_t>(), s));
     void* dTmp = nullptr;
-    SPARSE_ALLOC(pool, dTmp, tmpBytes, "reduce storage");
-    HPSDF_HIP(rocprim::reduce(dTmp, tmpBytes, ActiveCount(dClass, IsActive()), (uint64_t*)(dScalars + 1), (uint64_t)0, (size_t)g.nBlocks,
-                              rocprim::plus<uint64_t>(), s));
+    if (const int rc = withTemp(pool, "rocprim::reduce", "reduce storage", dTmp, tmpBytes, [&](void* tmp, size_t& bytes) {
+            return rocprim::reduce(tmp, bytes, ActiveCount(dClass, IsActive()), (uint64_t*)(dScalars + 1), (uint64_t)0, (size_t)g.nBlocks,
+                                   rocprim::plus<uint64_t>(), s);
+        }))
+        return rc;
     unsigned long long scal[2] = {0, 0};
     HPSDF_HIP(hipMemcpyAsync(scal, dScalars, sizeof scal, hipMemcpyDeviceToHost, s));
     HPSDF_HIP(hipStreamSynchronize(s));
@@ -666,20 +532,19 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
     uint64_t V = 0, T = 0;
     uint64_t *dActive = nullptr, *dVp = nullptr, *dTp = nullptr;
     if (nActive > 0) {
-        SPARSE_ALLOC(pool, dActive, nActive * 8, "active blocks");
-        tmpBytes = 0;
-        HPSDF_HIP(rocprim::select(nullptr, tmpBytes, rocprim::counting_iterator<uint64_t>(0), ActiveFlag(dClass, IsActiveFlag()), dActive,
-                                  (uint64_t*)(dScalars + 2), (size_t)g.nBlocks, s));
-        SPARSE_ALLOC(pool, dTmp, tmpBytes, "select storage");
-        HPSDF_HIP(rocprim::select(dTmp, tmpBytes, rocprim::counting_iterator<uint64_t>(0), ActiveFlag(dClass, IsActiveFlag()), dActive,
-                                  (uint64_t*)(dScalars + 2), (size_t)g.nBlocks, s));
+        SURF_ALLOC(pool, dActive, nActive * 8, "active blocks");
+        if (const int rc = withTemp(pool, "rocprim::select", "select storage", dTmp, tmpBytes, [&](void* tmp, size_t& bytes) {
+                return rocprim::select(tmp, bytes, rocprim::counting_iterator<uint64_t>(0), ActiveFlag(dClass, IsActiveFlag()), dActive,
+                                       (uint64_t*)(dScalars + 2), (size_t)g.nBlocks, s);
+            }))
+            return rc;
         ev.mark(2, s);
         // per-block counts and their prefixes
         uint32_t *dVc = nullptr, *dTc = nullptr;
-        SPARSE_ALLOC(pool, dVc, (nActive + 1) * 4, "vertex counts");
-        SPARSE_ALLOC(pool, dTc, (nActive + 1) * 4, "triangle counts");
-        SPARSE_ALLOC(pool, dVp, (nActive + 1) * 8, "vertex prefixes");
-        SPARSE_ALLOC(pool, dTp, (nActive + 1) * 8, "triangle prefixes");
+        SURF_ALLOC(pool, dVc, (nActive + 1) * 4, "vertex counts");
+        SURF_ALLOC(pool, dTc, (nActive + 1) * 4, "triangle counts");
+        SURF_ALLOC(pool, dVp, (nActive + 1) * 8, "vertex prefixes");
+        SURF_ALLOC(pool, dTp, (nActive + 1) * 8, "triangle prefixes");
         HPSDF_HIP(hipMemsetAsync(dVc + nActive, 0, 4, s));
         HPSDF_HIP(hipMemsetAsync(dTc + nActive, 0, 4, s));
         BlockOut o{};
@@ -689,13 +554,8 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
         HPSDF_HIP(hipStreamSynchronize(s));  // (select's storage is free again)
         pool.release(dTmp);
         pool.release(dClass);
-        dClass = nullptr;
-        tmpBytes = 0;
-        HPSDF_HIP(rocprim::exclusive_scan(nullptr, tmpBytes, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(nActive + 1),
-                                          rocprim::plus<uint64_t>(), s));
-        SPARSE_ALLOC(pool, dTmp, tmpBytes, "scan storage");
-        HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpBytes, dVc, dVp, (uint64_t)0, (size_t)(nActive + 1), rocprim::plus<uint64_t>(), s));
-        HPSDF_HIP(rocprim::exclusive_scan(dTmp, tmpBytes, dTc, dTp, (uint64_t)0, (size_t)(nActive + 1), rocprim::plus<uint64_t>(), s));
+        if (const int rc = withTemp(pool, kPrefixScan, "scan storage", dTmp, tmpBytes, prefixScan(dVc, dVp, nActive + 1, s))) return rc;
+        if (const int rc = primStatus(prefixScan(dTc, dTp, nActive + 1, s)(dTmp, tmpBytes), kPrefixScan)) return rc;  // (the same size: the same storage)
         ev.mark(4, s);
         HPSDF_HIP(hipMemcpyAsync(&V, dVp + nActive, 8, hipMemcpyDeviceToHost, s));
         HPSDF_HIP(hipMemcpyAsync(&T, dTp + nActive, 8, hipMemcpyDeviceToHost, s));
@@ -708,20 +568,18 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
         st.classify_ms = ev.ms(0, 1);
     }
 
-    HostOut hv, ht;
+    MeshOut mesh;
     if (T > 0) {
-        hv.p = std::malloc(V * 3 * sizeof(double));
-        ht.p = std::malloc(T * 3 * sizeof(uint64_t));
-        if (!hv.p || !ht.p) return fail(HPSDF_ERR_OUT_OF_MEMORY, std::string(kWhat) + ": host allocation failed");
+        if (const int rc = mesh.alloc(kWhat, V, T)) return rc;
         // records
         BlockOut o{};
         o.vprefix = dVp, o.tprefix = dTp;
-        SPARSE_ALLOC(pool, o.vkey, V * 8, "vertex keys");
-        SPARSE_ALLOC(pool, o.vidx, V * 8, "vertex indices");
-        SPARSE_ALLOC(pool, o.vxyz, V * 24, "vertex records");
-        SPARSE_ALLOC(pool, o.tkey, T * 8, "triangle keys");
-        SPARSE_ALLOC(pool, o.tidx, T * 8, "triangle indices");
-        SPARSE_ALLOC(pool, o.tedge, T * 24, "triangle records");
+        SURF_ALLOC(pool, o.vkey, V * 8, "vertex keys");
+        SURF_ALLOC(pool, o.vidx, V * 8, "vertex indices");
+        SURF_ALLOC(pool, o.vxyz, V * 24, "vertex records");
+        SURF_ALLOC(pool, o.tkey, T * 8, "triangle keys");
+        SURF_ALLOC(pool, o.tidx, T * 8, "triangle indices");
+        SURF_ALLOC(pool, o.tedge, T * 24, "triangle records");
         ev.mark(5, s);
         HPSDF_HIP(launchBlocks<true>(s, td, ctx->dTables, g, iso, dActive, nActive, o));
         ev.mark(6, s);
@@ -729,13 +587,13 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
         uint64_t *dVkS = nullptr, *dViS = nullptr, *dTkS = nullptr, *dTiS = nullptr;
         double* dVerts = nullptr;
         uint64_t* dTris = nullptr;
-        const unsigned vBits = bitsFor(3 * nPts), tBits = bitsFor(8 * nCubes);
-        SPARSE_ALLOC(pool, dVkS, V * 8, "sorted vertex keys");
-        SPARSE_ALLOC(pool, dViS, V * 8, "sorted vertex indices");
-        tmpBytes = 0;
-        HPSDF_HIP(rocprim::radix_sort_pairs(nullptr, tmpBytes, o.vkey, dVkS, o.vidx, dViS, (size_t)V, 0u, vBits, s));
-        SPARSE_ALLOC(pool, dTmp, tmpBytes, "sort storage");
-        HPSDF_HIP(rocprim::radix_sort_pairs(dTmp, tmpBytes, o.vkey, dVkS, o.vidx, dViS, (size_t)V, 0u, vBits, s));
+        const unsigned vBits = bitsFor(3 * cl.nPts), tBits = bitsFor(8 * cl.nCubes);
+        SURF_ALLOC(pool, dVkS, V * 8, "sorted vertex keys");
+        SURF_ALLOC(pool, dViS, V * 8, "sorted vertex indices");
+        if (const int rc = withTemp(pool, "rocprim::radix_sort_pairs", "sort storage", dTmp, tmpBytes, [&](void* tmp, size_t& bytes) {
+                return rocprim::radix_sort_pairs(tmp, bytes, o.vkey, dVkS, o.vidx, dViS, (size_t)V, 0u, vBits, s);
+            }))
+            return rc;
         HPSDF_HIP(hipStreamSynchronize(s));
         pool.release(dTmp);
         pool.release(o.vkey);
@@ -743,16 +601,16 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
         pool.release(dActive);
         pool.release(dVp);
         pool.release(dTp);
-        SPARSE_ALLOC(pool, dVerts, V * 24, "vertices");
-        hipLaunchKernelGGL(sparse_gather_kernel, dim3(gridOf(V)), dim3(kThreads), 0, s, dViS, o.vxyz, V, dVerts);
+        SURF_ALLOC(pool, dVerts, V * 24, "vertices");
+        hipLaunchKernelGGL(sparse_gather_kernel, dim3(gridOf(V)), dim3(kSurfThreads), 0, s, dViS, o.vxyz, V, dVerts);
         HPSDF_HIP(hipGetLastError());
         // triangles in key order, renumbered
-        SPARSE_ALLOC(pool, dTkS, T * 8, "sorted triangle keys");
-        SPARSE_ALLOC(pool, dTiS, T * 8, "sorted triangle indices");
-        tmpBytes = 0;
-        HPSDF_HIP(rocprim::radix_sort_pairs(nullptr, tmpBytes, o.tkey, dTkS, o.tidx, dTiS, (size_t)T, 0u, tBits, s));
-        SPARSE_ALLOC(pool, dTmp, tmpBytes, "sort storage");
-        HPSDF_HIP(rocprim::radix_sort_pairs(dTmp, tmpBytes, o.tkey, dTkS, o.tidx, dTiS, (size_t)T, 0u, tBits, s));
+        SURF_ALLOC(pool, dTkS, T * 8, "sorted triangle keys");
+        SURF_ALLOC(pool, dTiS, T * 8, "sorted triangle indices");
+        if (const int rc = withTemp(pool, "rocprim::radix_sort_pairs", "sort storage", dTmp, tmpBytes, [&](void* tmp, size_t& bytes) {
+                return rocprim::radix_sort_pairs(tmp, bytes, o.tkey, dTkS, o.tidx, dTiS, (size_t)T, 0u, tBits, s);
+            }))
+            return rc;
         HPSDF_HIP(hipStreamSynchronize(s));
         pool.release(dTmp);
         pool.release(o.tkey);
@@ -760,18 +618,15 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
         pool.release(dTkS);
         pool.release(o.vxyz);
         pool.release(dViS);
-        SPARSE_ALLOC(pool, dTris, T * 24, "triangles");
-        hipLaunchKernelGGL(sparse_renumber_kernel, dim3(gridOf(T)), dim3(kThreads), 0, s, dTiS, o.tedge, T, dVkS, V, dTris);
+        SURF_ALLOC(pool, dTris, T * 24, "triangles");
+        hipLaunchKernelGGL(sparse_renumber_kernel, dim3(gridOf(T)), dim3(kSurfThreads), 0, s, dTiS, o.tedge, T, dVkS, V, dTris);
         HPSDF_HIP(hipGetLastError());
         ev.mark(7, s);
-        HPSDF_HIP(hipMemcpyAsync(hv.p, dVerts, V * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HPSDF_HIP(hipMemcpyAsync(ht.p, dTris, T * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if (const int rc = mesh.download(dVerts, dTris, s)) return rc;
         ev.mark(8, s);
         HPSDF_HIP(hipStreamSynchronize(s));
         st.emit_ms = ev.ms(5, 6), st.sort_ms = ev.ms(6, 7), st.download_ms = ev.ms(7, 8), st.total_ms = ev.ms(0, 8);
-        *verts = (double*)hv.p, *tris = (uint64_t*)ht.p;
-        hv.p = nullptr, ht.p = nullptr;
-        *nVerts = V, *nTris = T;
+        mesh.handOver(verts, nVerts, tris, nTris);
     } else {
         ev.mark(8, s);
         HPSDF_HIP(hipStreamSynchronize(s));
@@ -844,7 +699,7 @@ int hpsdf_surface_classify_host(const void* block, size_t size, const double lo[
     HostTree ht;
     if (const int rc = parseBlock(block, size, &ht)) return rc;
     SparseLattice g{};
-    if (const int rc = makeLattice(kWhat, ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
+    if (const int rc = makeLattice(kWhat, ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, iso, &g)) return rc;
     if (first_block > g.nBlocks || count > g.nBlocks - first_block)
         return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
     const HostEval eval{&tables()};
@@ -864,15 +719,15 @@ int hpsdf_surface_classify_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const dou
     if (!t || !lo || !hi || !n || (!out && count)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
     if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
     SparseLattice g{};
-    if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g, nullptr, nullptr)) return rc;
+    if (const int rc = makeLattice(kWhat, t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, iso, &g)) return rc;
     if (first_block > g.nBlocks || count > g.nBlocks - first_block)
         return fail(HPSDF_ERR_INVALID_ARGUMENT, std::string(kWhat) + ": the block range ends past the lattice's blocks");
     if (count == 0) return HPSDF_OK;
     HPSDF_HIP(hipSetDevice(ctx->device));
-    DevPool pool;
+    DevPool pool(kWhat);
     uint8_t* dClass = nullptr;
-    SPARSE_ALLOC(pool, dClass, (size_t)count, "block classes");
-    if (const int rc = classifyOnDevice(kWhat, ctx, t, pool, g, iso, first_block, count, dClass, nullptr)) return rc;
+    SURF_ALLOC(pool, dClass, (size_t)count, "block classes");
+    if (const int rc = classifyOnDevice(ctx, t, pool, g, iso, first_block, count, dClass, nullptr)) return rc;
     HPSDF_HIP(hipMemcpyAsync(out, dClass, (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
     HPSDF_HIP(hipStreamSynchronize(ctx->stream));
     return HPSDF_OK;

@@ -3,7 +3,7 @@ alternating, at n = 256, 512 and 1000 cubes per axis (the dense call's range), s
 the repetitions of the call's wall time (it ends in a device synchronise and the download) and of the device milliseconds of each
 phase (hpsdf_surface_last_timings / the sparse call's stats), the active share of the blocks, peak device scratch, output sizes, and
 whether the two calls' arrays are equal.  Writes profiles/surface_sparse.json and prints the same JSON line.
-    usage: python tools/surface_sparse_bench.py [--reps R] [--max-n N] [--out PATH]"""
+    usage: python tools/surface_sparse_bench.py [--reps R] [--max-n N] [--out PATH] [--targets 1e-5,1e-7]   (the trees, in this order)"""
 import json
 import os
 import sys
@@ -36,7 +36,7 @@ def main():
         raise SystemExit("surface_sparse_bench: no GPU (nothing is measured without one)")
     ctx = H.Context(0)
     rows = []
-    for target in (1e-5, 1e-7):
+    for target in [float(x) for x in arg("--targets", "1e-5,1e-7").split(",")]:
         blk, _ = H.create_block(ctx, H.make_config(target), H.Field.union3(), 0)
         tree = H.DeviceTree(ctx, blk)
         info = tree.info()
