@@ -345,18 +345,22 @@ uint64_t ora_weight_key(const float bmin[3], int depth, int degree) {
     const uint64_t b = (uint64_t)f32_bits(bmin[2]) | ((uint64_t)(unsigned)depth << 32) | ((uint64_t)(unsigned)degree << 40);
     return splitmix64(a) ^ splitmix64(b ^ 0xD1B54A32D192ED03ull);
 }
+/* Sample point i of the fit (cell, depth, degree): the stand-in for aabb.sample().cast<f64>() */
+void ora_weight_point(const float bmin[3], const float bmax[3], int depth, int degree, uint64_t i, double pt[3]) {
+    const uint64_t key = ora_weight_key(bmin, depth, degree);
+    for (int a = 0; a < 3; ++a) {
+        /* AlignedBox3f::sample(): min + (max - min) * r in f32, then cast<f64>() */
+        const float r = (float)(splitmix64(key + (i * 3 + (uint64_t)a) * 0x9E3779B97F4A7C15ull) >> 40) * (1.0f / 16777216.0f);
+        pt[a] = (double)(bmin[a] + (bmax[a] - bmin[a]) * r);
+    }
+}
 /* |mean of FApprox over the 100 sample points| (:1215-1222 / :1236-1243) */
 double ora_weight_mean(const double* coeffs, int degree, const float bmin[3], const float bmax[3], int depth) {
-    const uint64_t key = ora_weight_key(bmin, depth, degree);
     const uint64_t nSamples = 100;
     double fIntegral = 0.0;
     for (uint64_t i = 0; i < nSamples; ++i) {
         double pt[3];
-        for (int a = 0; a < 3; ++a) {
-            /* AlignedBox3f::sample(): min + (max - min) * r in f32, then cast<f64>() */
-            const float r = (float)(splitmix64(key + (i * 3 + (uint64_t)a) * 0x9E3779B97F4A7C15ull) >> 40) * (1.0f / 16777216.0f);
-            pt[a] = (double)(bmin[a] + (bmax[a] - bmin[a]) * r);
-        }
+        ora_weight_point(bmin, bmax, depth, degree, i, pt);
         fIntegral += ora_fapprox(coeffs, degree, bmin, bmax, pt, depth);
     }
     fIntegral /= (double)nSamples;

@@ -126,6 +126,7 @@ double ora_fit_polynomial(const ora_field* f, const ora_config* cfg, double* coe
 /* Nearness weighting, Octree.cpp:1209-1247, with a deterministic stand-in for aabb.sample() (std::rand in the
  * reference): parity unpinned, see hp_oracle.c */
 uint64_t ora_weight_key(const float bmin[3], int depth, int degree);
+void ora_weight_point(const float bmin[3], const float bmax[3], int depth, int degree, uint64_t i, double pt[3]);
 double ora_weight_mean(const double* coeffs, int degree, const float bmin[3], const float bmax[3], int depth);
 double ora_weight_from_mean(int type, double strength, double mean);
 double ora_poly_weighting(const double* coeffs, int degree, const float bmin[3], const float bmax[3], int depth, double strength);

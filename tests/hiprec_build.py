@@ -62,10 +62,22 @@ No number below was chosen by looking at a kernel's or the oracle's output.
    formed with the rule of order 4q + 1 (:1012-1017); nothing is copied or refitted.  (COUNT[6] = 83 stops one short, so row 83 =
    (6, 0, 0) is formed by the degree-7 fit.)  check_leaf_rows compares each range with fit_reference of that degree, each row
    within that fit's "bound" (one bound for every fit mode, hiprec.py section 2).
+
+6. Nearness weighting (Config::nearnessWeighting, :1071-1092).  replay_free and Guided take weighting = (type, strength); every
+   error above is then FitPolynomial's return value, the fit's error times the weight of the array that fit produced
+   (hiprec_weight.py: the sampler's definition, the long-double mean of the array the fit history of section 5 gives, the weight
+   and the bound of each).  Each of a job's nine errors is weighted with its own array: p_err with the P array -- the node's copied
+   rows (:847) and the appended ones, at the job's depth, sampler degree p + 1 -- and h_err[i] with child i's from-scratch array at
+   depth d + 1, sampler degree p.  A coarse job weights p_err alone, with its degree-2 array; its eight other header slots belong
+   to no fit and check_round requires +0.0 there.  Sections 2 to 4 run unchanged on the weighted errors and their bounds: the
+   decisions, the selection, the totals, B and the stop's consistency.  Section 5 applies as it stands: weighting changes no row,
+   and a weighted build's rows have the provenance of an unweighted one's -- which is what shows a stale copied row.
+   WEIGHT_MUTANTS are defects of this section alone (tests/test_hiprec_weight_cpu.py shows each one rejected).
 """
 import numpy as np
 
 import hiprec as R
+import hiprec_weight as W
 
 LD, U, SLACK = R.LD, R.U, R.SLACK
 COUNT = R.COUNT
@@ -74,7 +86,9 @@ COARSE_DEPTH, COARSE_DEGREE = 4, 2
 MAX_DEPTH, MAX_DEGREE = 10, 12
 INTERIOR = R.INTERIOR
 K_IMP = 3
-MUTANTS = ("swap_divisors", "no8_p", "no8_h", "mean_child", "child_degree+1", "child_nl_parent", "apply_desc")
+SCHEDULE_MUTANTS = ("swap_divisors", "no8_p", "no8_h", "mean_child", "child_degree+1", "child_nl_parent", "apply_desc")
+WEIGHT_MUTANTS = W.MUTANTS                                  # section 6; they change nothing in an unweighted build
+MUTANTS = SCHEDULE_MUTANTS + WEIGHT_MUTANTS
 
 
 # ---------------------------------------------------------------------------------------------------------------- geometry
@@ -188,7 +202,8 @@ class Fits:
 def _job_fits(lo, hi, degree, depth, coarse, mutant):
     """The fits a job needs -> (p fit or None, list of eight child fits or None), each (lo, hi, degree, depth, nl)."""
     if coarse:
-        return (lo, hi, COARSE_DEGREE, depth, None), None
+        hf = [corner_aabb(lo, hi, i) + (COARSE_DEGREE, depth + 1, None) for i in range(8)] if mutant == "w_coarse_nine" else None
+        return (lo, hi, COARSE_DEGREE, depth, None), hf
     pf = (lo, hi, degree + 1, depth, None) if degree < MAX_DEGREE - 1 else None
     hf = None
     if depth < MAX_DEPTH:
@@ -198,13 +213,32 @@ def _job_fits(lo, hi, degree, depth, coarse, mutant):
     return pf, hf
 
 
-def job_errors(fits, jobs, mutant=None):
-    """jobs: [(lo, hi, degree, depth, coarse)] -> per job (p, h): p = (e, bound) or None, h = [(e, bound)] * 8 or None."""
-    need = [_job_fits(*j, mutant) for j in jobs]
+def job_errors(fits, jobs, mutant=None, weighting=None):
+    """jobs: [(lo, hi, degree, depth, coarse, p0)] -> per job (p, h): p = (e, bound) or None, h = [(e, bound)] * 8 or None.  With
+    a weighting (a W.Weighting) every error is its fit's times the weight of its own array (section 6); p0 is the degree of the
+    from-scratch fit that began the node's array (section 5), which says where a P array's rows come from."""
+    need = [_job_fits(*j[:5], mutant) for j in jobs]
     fits.ensure([f for pf, hf in need for f in ([pf] if pf else []) + (hf or [])])
     out = []
     for pf, hf in need:
         out.append((fits.get(*pf)[:2] if pf else None, [fits.get(*f)[:2] for f in hf] if hf else None))
+    if weighting is None:
+        return out
+    items, where = [], []
+    for n, ((lo, hi, degree, depth, coarse, p0), (pf, hf)) in enumerate(zip(jobs, need)):
+        if pf:
+            items.append((lo, hi, depth, COARSE_DEGREE, COARSE_DEGREE, "C") if coarse else (lo, hi, depth, p0, degree + 1, "P"))
+            where.append((n, -1))
+        for i, f in enumerate(hf or []):
+            own = (f[0], f[1], f[3], f[2], f[2], "H")
+            items.append((lo, hi, depth, p0, degree, "H") if mutant == "w_child_parent" and not coarse else own)
+            where.append((n, i))
+    for (n, i), (w, wb) in zip(where, weighting.weights(fits, items)):
+        p, h = out[n]
+        if i < 0:
+            out[n] = (W.weighted_error(p[0], p[1], w, wb), h)
+        else:
+            h[i] = W.weighted_error(h[i][0], h[i][1], w, wb)
     return out
 
 
@@ -293,8 +327,9 @@ def true_total(errs):
 
 # ---------------------------------------------------------------------------------------------------------------- the tree under replay
 class _State:
-    def __init__(self, spec, root, left, fits):
+    def __init__(self, spec, root, left, fits, weighting=None, mutant=None):
         self.fits = fits if fits is not None else Fits(spec, root, left)
+        self.weighting = weighting if weighting is None or isinstance(weighting, W.Weighting) else W.Weighting(*weighting, mutant=mutant)
         self.t, coarse = coarse_tree()
         self.queue = {n: (LD(INITIAL_NODE_ERR), 0.0) for n in coarse}     # node -> (reference error, bound)
         self.dropped = {}
@@ -302,7 +337,7 @@ class _State:
         self.counts = {"rounds": 0, "jobs": 0, "p_refines": 0, "h_refines": 0, "dropped": 0}
 
     def job_tuple(self, n, coarse):
-        return (self.t.bmin[n], self.t.bmax[n], self.t.degree[n], self.t.depth[n], coarse)
+        return (self.t.bmin[n], self.t.bmax[n], self.t.degree[n], self.t.depth[n], coarse, COARSE_DEGREE if coarse else self.hist[n][0])
 
     def apply(self, n, action, coarse, p, h):
         """One result (:253-290) on the tree and the queue; the caller moves the totals."""
@@ -338,15 +373,17 @@ class _State:
 
     def result(self):
         out = self.t.arrays()
-        out.update(history={n: (p0, tuple(app)) for n, (p0, app) in self.hist.items()}, counts=dict(self.counts), fits=self.fits)
+        out.update(history={n: (p0, tuple(app)) for n, (p0, app) in self.hist.items()}, counts=dict(self.counts), fits=self.fits,
+                   weighting=self.weighting)
         return out
 
 
-def replay_free(spec, root, target, K, rounds, left=False, mutant=None, fits=None):
+def replay_free(spec, root, target, K, rounds, left=False, mutant=None, fits=None, weighting=None):
     """Grow the tree from long-double errors alone for exactly `rounds` rounds (section 4: the stop itself is not decidable) ->
     dict(child, degree, depth, bmin, bmax, history, counts, undecided_decisions, undecided_selections, min_margin,
-    stop_consistent, true_total, true_bound, B, fits)."""
-    s = _State(spec, root, left, fits)
+    stop_consistent, true_total, true_bound, B, fits, weighting).  weighting: None, (type, strength) or a W.Weighting (its cache
+    of weights is then shared): every error below is the weighted one (section 6)."""
+    s = _State(spec, root, left, fits, weighting, mutant)
     tot = Totals(False)
     undecided_d = undecided_s = 0
     min_margin, consistent = np.inf, True
@@ -362,7 +399,7 @@ def replay_free(spec, root, target, K, rounds, left=False, mutant=None, fits=Non
                 undecided_s += 1
         take = sorted(take, reverse=(mutant == "apply_desc"))
         coarse = r == 0
-        errs = job_errors(s.fits, [s.job_tuple(n, coarse) for n in take], mutant)
+        errs = job_errors(s.fits, [s.job_tuple(n, coarse) for n in take], mutant, s.weighting)
         for n, (p, h) in zip(take, errs):
             e, eb = s.queue[n]
             d = decide(e, eb, p, h, s.t.degree[n], s.t.depth[n], coarse, mutant)
@@ -387,8 +424,8 @@ def replay_free(spec, root, target, K, rounds, left=False, mutant=None, fits=Non
 class Guided:
     """check_round for the stepwise API: follows the product's selections round by round and checks everything else."""
 
-    def __init__(self, spec, root, target, K, left=False, mutant=None, fits=None):
-        self.s = _State(spec, root, left, fits)
+    def __init__(self, spec, root, target, K, left=False, mutant=None, fits=None, weighting=None):
+        self.s = _State(spec, root, left, fits, weighting, mutant)
         self.target, self.K, self.mutant = target, K, mutant
         self.tot = Totals(True)
         self.q64 = {n: np.float64(INITIAL_NODE_ERR) for n in self.s.queue}      # the float64 errors the product queued
@@ -428,7 +465,7 @@ class Guided:
             a, c = s.queue[order[want - 1]], s.queue[order[want]]
             self.worst["selection_ties"] += float(a[0] - c[0]) <= a[1] + c[1]
         # errors and decisions (section 2)
-        errs = job_errors(s.fits, [s.job_tuple(n, coarse) for n in sel], self.mutant)
+        errs = job_errors(s.fits, [s.job_tuple(n, coarse) for n in sel], self.mutant, s.weighting)
         acts = []
         for (n, _, _, err, degree, depth, _), hdr, (p, h) in zip(jobs, headers, errs):
             live = ([(hdr[0], p)] if p else []) + ([(hdr[1 + i], h[i]) for i in range(8)] if h else [])
@@ -436,6 +473,10 @@ class Guided:
                 ratio = float(abs(LD(got) - ev)) / bv if bv > 0 else (0.0 if LD(got) == ev else np.inf)
                 self.worst["job_error"] = max(self.worst["job_error"], ratio)
                 assert ratio <= 1, "round %d: node %d: an error is %.3g bounds from the reference" % (r, n, ratio)
+            if s.weighting is not None and coarse and h is None:
+                # section 6: a coarse job's eight other slots belong to no fit; nothing may have been weighted into them
+                assert all(np.float64(v).tobytes() == np.float64(0.0).tobytes() for v in hdr[1:9]), \
+                    "round %d: node %d: a header slot that belongs to no fit is not +0.0" % (r, n)
             ev, eb = s.queue[n]
             d = decide(ev, eb, p, h, s.t.degree[n], s.t.depth[n], coarse, self.mutant)
             act = decide_f64(err, hdr, s.t.degree[n], s.t.depth[n], coarse)
@@ -473,7 +514,7 @@ class Guided:
         assert drift <= self.tot.B + tb, (drift, self.tot.B, tb)
         out = dict(self.worst)
         out.update(drift=drift, B=self.tot.B, drift_over_B=drift / self.tot.B, true_total=tt, true_bound=tb, f64_total=float(self.tot.f64),
-                   small_rounds=self.small_rounds, history=s.result()["history"], counts=dict(s.counts))
+                   small_rounds=self.small_rounds, history=s.result()["history"], counts=dict(s.counts), weighting=s.weighting)
         return out
 
 

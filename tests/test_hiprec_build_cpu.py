@@ -221,7 +221,7 @@ def _free_differs(O, name, **kw):
     return False
 
 
-@pytest.mark.parametrize("mutant", ["K+1", "K-1"] + list(B.MUTANTS))
+@pytest.mark.parametrize("mutant", ["K+1", "K-1"] + list(B.SCHEDULE_MUTANTS))
 def test_mutants_of_the_replay_are_caught(H, O, mutant):
     """Each mutant of the replay -- K + 1, K - 1, the two divisors swapped, the factor 8 dropped from either improvement, the mean
     child error for the max, children fitted at degree + 1, child errors normalised at the parent's depth, results applied in
