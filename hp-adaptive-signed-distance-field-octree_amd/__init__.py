@@ -178,6 +178,18 @@ _SIGNATURES = {
     "hpsdf_cast_rays_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "hpsdf_query_bounds_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "hpsdf_query_bounds_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "hpsdf_query_bounds_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "hpsdf_query_bounds_grid_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_query_bounds_grid_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_query_bounds_grid_block": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                                C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -711,6 +723,43 @@ class DeviceTree:
                                            vp(d_out_status_ptr), vp(d_out_t_ptr), vp(d_out_xyz_ptr), vp(d_out_val_ptr), vp(d_out_grad_ptr),
                                            vp(d_out_evals_ptr), vp(d_out_cells_ptr)))
 
+    def query_bounds(self, boxes, subdiv=1, max_leaves=4096):
+        """QueryBounds (include/hpsdf.h): for each box (a row of six doubles: lower corner, upper corner, world coordinates) an interval
+        that holds Query(x) for every point x of the box -> (lo f64 [n], hi f64 [n], status u8 [n], leaves u32 [n]).  status:
+        BOUNDS_OK; BOUNDS_LEAF_LIMIT (more than max_leaves leaves: [-inf, inf]); BOUNDS_INVALID (a corner outside the root, a NaN,
+        a > b: NaNs); BOUNDS_NOT_FINITE (a leaf with a non-finite coefficient: [-inf, inf]).  subdiv 2 or 4 splits a leaf's part of
+        the box that many times per axis: tighter, at 8 or 64 evaluations a leaf."""
+        b = _box_array(boxes)
+        bufs = _bounds_outputs(len(b))
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().hpsdf_query_bounds_host(self.ctx.handle, self.handle, vp(b), len(b), _max_iter(subdiv), _max_iter(max_leaves),
+                                            *[vp(x) for x in bufs]))
+        return bufs
+
+    def query_bounds_device(self, d_boxes_ptr, n, d_out_lo_ptr, d_out_hi_ptr, d_out_status_ptr, d_out_leaves_ptr=0, subdiv=1, max_leaves=4096):
+        """Raw device pointers (ints; 0 = NULL for d_out_leaves_ptr only); asynchronous on the context stream."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        check(lib().hpsdf_query_bounds_device(self.ctx.handle, self.handle, vp(d_boxes_ptr), n, _max_iter(subdiv), _max_iter(max_leaves),
+                                              vp(d_out_lo_ptr), vp(d_out_hi_ptr), vp(d_out_status_ptr), vp(d_out_leaves_ptr)))
+
+    def query_bounds_grid(self, lo, hi, n, subdiv=1, max_leaves=4096):
+        """query_bounds over the cells of the lattice of n[a] cells per axis on [lo, hi] (extract_surface's lattice; no box array is
+        made) -> (lo, hi, status, leaves) shaped [n2, n1, n0]."""
+        lo3, hi3, n3 = _lattice_args(lo, hi, n)
+        shape = (int(n[2]), int(n[1]), int(n[0]))
+        bufs = _bounds_outputs(shape)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(lib().hpsdf_query_bounds_grid_host(self.ctx.handle, self.handle, lo3, hi3, n3, _max_iter(subdiv), _max_iter(max_leaves),
+                                                 *[vp(x) for x in bufs]))
+        return bufs
+
+    def query_bounds_grid_device(self, lo, hi, n, d_out_lo_ptr, d_out_hi_ptr, d_out_status_ptr, d_out_leaves_ptr=0, subdiv=1, max_leaves=4096):
+        """Raw device pointers for the n0 n1 n2 rows (x fastest); asynchronous on the context stream."""
+        lo3, hi3, n3 = _lattice_args(lo, hi, n)
+        vp = lambda p: C.c_void_p(p) if p else None
+        check(lib().hpsdf_query_bounds_grid_device(self.ctx.handle, self.handle, lo3, hi3, n3, _max_iter(subdiv), _max_iter(max_leaves),
+                                                   vp(d_out_lo_ptr), vp(d_out_hi_ptr), vp(d_out_status_ptr), vp(d_out_leaves_ptr)))
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1150,6 +1199,24 @@ class Octree:
             return int(st[0]), float(t[0]), pts[0], float(val[0]), grad[0], int(evals[0]), int(cells[0])
         return st, t, pts, val, grad, evals, cells
 
+    def QueryBounds(self, boxes, subdiv=1, max_leaves=4096):
+        """An interval that holds Query over each whole box (DeviceTree.query_bounds): one box (6,) = lower corner then upper corner
+        -> (lo, hi, status, leaves) with scalars, or (n,6) -> the four arrays.  lo > 0 proves the box outside the surface, hi < 0
+        inside it; no sampling density can."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        b = np.asarray(boxes, np.float64)
+        lo, hi, st, leaves = self._tree.query_bounds(b, subdiv, max_leaves)
+        return (float(lo[0]), float(hi[0]), int(st[0]), int(leaves[0])) if b.ndim == 1 else (lo, hi, st, leaves)
+
+    def QueryBoundsGrid(self, view_min, view_max, n, subdiv=1, max_leaves=4096):
+        """QueryBounds over the cells of the lattice of n cells per axis (an int or three) on [view_min, view_max]
+        (DeviceTree.query_bounds_grid) -> (lo, hi, status, leaves), each shaped [n2, n1, n0]."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
+        return self._tree.query_bounds_grid(view_min, view_max, n3, subdiv, max_leaves)
+
     def QueryRay(self, origins, directions, t_max):
         """Octree::QueryRay (Octree.h:75) for one ray -> (hit, t) or (n,3) arrays -> (hit[n], t[n])."""
         if self._tree is None:
@@ -1291,6 +1358,41 @@ def cast_rays_block(block, origins, directions, t_max, iso=0.0, tol=1e-9, max_it
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     check(lib().hpsdf_cast_rays_block(buf, len(buf), vp(o), vp(d), vp(tm), n, float(iso), float(tol), _max_iter(max_iter),
                                       _max_iter(max_cells), CAST_UNIT if unit else 0, *[vp(b) for b in bufs]))
+    return bufs
+
+
+BOUNDS_OK, BOUNDS_LEAF_LIMIT, BOUNDS_INVALID, BOUNDS_NOT_FINITE = 0, 1, 2, 3  # HPSDF_BOUNDS_*: out_status
+
+
+def _box_array(boxes):
+    b = np.ascontiguousarray(boxes, np.float64)
+    if b.size % 6:
+        raise ValueError("a box is six doubles: the lower corner, then the upper corner")
+    return b.reshape(-1, 6)
+
+
+def _bounds_outputs(shape):
+    return np.empty(shape), np.empty(shape), np.empty(shape, np.uint8), np.empty(shape, np.uint32)
+
+
+def query_bounds_block(block, boxes, subdiv=1, max_leaves=4096):
+    """hpsdf_query_bounds_block: DeviceTree.query_bounds' arrays from a serialised block on the calling thread (no device)
+    -> (lo f64 [n], hi f64 [n], status u8 [n], leaves u32 [n])."""
+    b = _box_array(boxes)
+    bufs = _bounds_outputs(len(b))
+    buf = bytes(block)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().hpsdf_query_bounds_block(buf, len(buf), vp(b), len(b), _max_iter(subdiv), _max_iter(max_leaves), *[vp(x) for x in bufs]))
+    return bufs
+
+
+def query_bounds_grid_block(block, lo, hi, n, subdiv=1, max_leaves=4096):
+    """hpsdf_query_bounds_grid_block: DeviceTree.query_bounds_grid's arrays [n2, n1, n0] from a serialised block (no device)."""
+    lo3, hi3, n3 = _lattice_args(lo, hi, n)
+    bufs = _bounds_outputs((int(n[2]), int(n[1]), int(n[0])))
+    buf = bytes(block)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().hpsdf_query_bounds_grid_block(buf, len(buf), lo3, hi3, n3, _max_iter(subdiv), _max_iter(max_leaves), *[vp(x) for x in bufs]))
     return bufs
 
 

@@ -24,6 +24,7 @@
 #include "launch.hpp"
 #include "ray_cast.hpp"
 #include "runtime.hpp"
+#include "tree_bound.hpp"
 
 using namespace hpsdf;
 
@@ -831,6 +832,7 @@ int hpsdf_tree_destroy(hpsdf_tree* t) {
     if (t->dTop) (void)hipFree(t->dTop);
     if (t->dTopRec) (void)hipFree(t->dTopRec);
     if (t->dCoeffs) (void)hipFree(t->dCoeffs);
+    if (t->dBoundConsts) (void)hipFree(t->dBoundConsts);
     delete t;
     return HPSDF_OK;
 }
@@ -1090,6 +1092,90 @@ int hpsdf_cast_rays_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* orig
         return hpsdf_cast_rays_device(ctx, t, dOrigins, dDirs, dTMax, n, iso, tol, maxIter, maxCells, flags, dOutStatus, dOutT, dOutXyz, dOutVal,
                                       dOutGrad, dOutEvals, dOutCells);
     });
+    HPSDF_CATCH
+}
+
+// QueryBounds (include/hpsdf.h): a guaranteed range of Query over boxes (query_bounds.hip, tree_bound.hpp, host_query.cpp).  The box and
+// the grid entries differ in where a box comes from and in nothing else: boxes == nullptr means the cells of *grid.
+static int boundsOnDevice(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dBoxes, const BoxGrid* grid, size_t n, uint32_t subdiv,
+                          uint32_t maxLeaves, double* dOutLo, double* dOutHi, uint8_t* dOutStatus, uint32_t* dOutLeaves) {
+    if (const int rc = treeOnContext(ctx, t)) return rc;
+    if (const int rc = t->boundConsts(ctx)) return rc;  // (built by the first call on this tree; a load and a branch afterwards)
+    ClsTree ct{t->dev.nodes, t->dev.coeffs, t->dBoundConsts, {}, {}};
+    for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
+    HPSDF_HIP(launchQueryBounds(ctx->stream, ct, t->maxDegree, ctx->dTables, dBoxes, grid, n, subdiv, maxLeaves, dOutLo, dOutHi, dOutStatus,
+                                dOutLeaves));
+    return HPSDF_OK;
+}
+
+static int boundsOnHost(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* boxes, const BoxGrid* grid, size_t n, uint32_t subdiv, uint32_t maxLeaves,
+                        double* outLo, double* outHi, uint8_t* outStatus, uint32_t* outLeaves) {
+    if (n <= kHostQueryPoints && smallQueriesOnHost()) {
+        if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+        if (const int hc = t->hostCopies()) return hc;
+        if (const int hc = t->boundHostCopies(ctx)) return hc;
+        ClsTree ct{t->hRecs.data(), t->hPadded.data(), t->hBoundConsts.data(), {}, {}};
+        for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
+        hostBoundsRows(ct, boxes, grid, n, subdiv, maxLeaves, outLo, outHi, outStatus, outLeaves);
+        return HPSDF_OK;
+    }
+    HostArrays arr;
+    const HostArrays::Dev<const double> dBoxes = boxes ? arr.in(boxes, n * 6) : HostArrays::Dev<const double>{nullptr};
+    const auto dOutLo = arr.out(outLo, n);
+    const auto dOutHi = arr.out(outHi, n);
+    const auto dOutStatus = arr.out(outStatus, n);
+    const auto dOutLeaves = arr.out(outLeaves, n);
+    return hostCall(ctx, arr, [&] { return boundsOnDevice(ctx, t, dBoxes, grid, n, subdiv, maxLeaves, dOutLo, dOutHi, dOutStatus, dOutLeaves); });
+}
+
+int hpsdf_query_bounds_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* dBoxes, size_t n, uint32_t subdiv, uint32_t maxLeaves,
+                              double* dOutLo, double* dOutHi, uint8_t* dOutStatus, uint32_t* dOutLeaves) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = boundsArgumentError(subdiv, maxLeaves, n, dBoxes, dOutLo, dOutHi, dOutStatus)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (n == 0) return HPSDF_OK;
+    return boundsOnDevice(ctx, t, dBoxes, nullptr, n, subdiv, maxLeaves, dOutLo, dOutHi, dOutStatus, dOutLeaves);
+    HPSDF_CATCH
+}
+
+int hpsdf_query_bounds_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* boxes, size_t n, uint32_t subdiv, uint32_t maxLeaves, double* outLo,
+                            double* outHi, uint8_t* outStatus, uint32_t* outLeaves) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = boundsArgumentError(subdiv, maxLeaves, n, boxes, outLo, outHi, outStatus)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (n == 0) return HPSDF_OK;
+    return boundsOnHost(ctx, t, boxes, nullptr, n, subdiv, maxLeaves, outLo, outHi, outStatus, outLeaves);
+    HPSDF_CATCH
+}
+
+int hpsdf_query_bounds_grid_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3],
+                                   uint32_t subdiv, uint32_t maxLeaves, double* dOutLo, double* dOutHi, uint8_t* dOutStatus,
+                                   uint32_t* dOutLeaves) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (!lo || !hi || !n) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const int rc = boundsArgumentError(subdiv, maxLeaves, 1, lo, dOutLo, dOutHi, dOutStatus)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    BoxGrid g{};
+    size_t count = 0;
+    if (const int rc = checkBoundsGrid("hpsdf_query_bounds_grid_device", t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, &g, &count)) return rc;
+    return boundsOnDevice(ctx, t, nullptr, &g, count, subdiv, maxLeaves, dOutLo, dOutHi, dOutStatus, dOutLeaves);
+    HPSDF_CATCH
+}
+
+int hpsdf_query_bounds_grid_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3], uint32_t subdiv,
+                                 uint32_t maxLeaves, double* outLo, double* outHi, uint8_t* outStatus, uint32_t* outLeaves) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (!lo || !hi || !n) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const int rc = boundsArgumentError(subdiv, maxLeaves, 1, lo, outLo, outHi, outStatus)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    BoxGrid g{};
+    size_t count = 0;
+    if (const int rc = checkBoundsGrid("hpsdf_query_bounds_grid_host", t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, &g, &count)) return rc;
+    return boundsOnHost(ctx, t, nullptr, &g, count, subdiv, maxLeaves, outLo, outHi, outStatus, outLeaves);
     HPSDF_CATCH
 }
 

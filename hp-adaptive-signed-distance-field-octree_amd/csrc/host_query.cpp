@@ -23,6 +23,7 @@
 #include "ray_cast.hpp"
 #include "runtime.hpp"
 #include "tables.hpp"
+#include "tree_bound.hpp"
 
 namespace hpsdf {
 
@@ -371,6 +372,44 @@ int castArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter, 
     return HPSDF_OK;
 }
 
+// QueryBounds (include/hpsdf.h) for n boxes: boundsWalk (tree_bound.hpp) with Query's leaf evaluation, the statements of
+// query_bounds_kernel.  boxes == nullptr: the cells of *grid.  outLeaves may be null.
+namespace {
+
+template <class Boxes>
+void boundsRows(const ClsTree& t, const Boxes& boxes, size_t n, uint32_t subdiv, uint32_t maxLeaves, double* outLo, double* outHi,
+                uint8_t* outStatus, uint32_t* outLeaves) {
+    const HostEval eval{&tables()};
+    HostBoundsStack st;
+    for (size_t i = 0; i < n; ++i) {
+        double a[3], b[3];
+        boxes.get(i, a, b);
+        BoundsRow r;
+        boundsWalk(t, a, b, subdiv, maxLeaves, eval, st, r);
+        outLo[i] = r.lo, outHi[i] = r.hi, outStatus[i] = (uint8_t)r.status;
+        if (outLeaves) outLeaves[i] = r.leaves;
+    }
+}
+
+}  // namespace
+
+void hostBoundsRows(const ClsTree& t, const double* boxes, const BoxGrid* grid, size_t n, uint32_t subdiv, uint32_t maxLeaves, double* outLo,
+                    double* outHi, uint8_t* outStatus, uint32_t* outLeaves) {
+    if (n == 0) return;  // (then both sources may be null)
+    if (boxes)
+        boundsRows(t, BoxArray{boxes}, n, subdiv, maxLeaves, outLo, outHi, outStatus, outLeaves);
+    else
+        boundsRows(t, *grid, n, subdiv, maxLeaves, outLo, outHi, outStatus, outLeaves);
+}
+
+// what hpsdf_query_bounds_* reject before anything runs (0: fine)
+int boundsArgumentError(uint32_t subdiv, uint32_t maxLeaves, size_t n, const void* in, const void* lo, const void* hi, const void* status) {
+    if (subdiv != 1u && subdiv != 2u && subdiv != 4u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_bounds: subdiv must be 1, 2 or 4");
+    if (maxLeaves < 1u || maxLeaves > 65535u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_query_bounds: max_leaves must be in 1..65535");
+    if (n && (!in || !lo || !hi || !status)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    return HPSDF_OK;
+}
+
 namespace {
 
 // What the *_block entries answer from: a serialised block as a host-only tree handle -- validated and laid out like the device mirror
@@ -452,6 +491,37 @@ extern "C" int hpsdf_cast_rays_block(const void* block, size_t size, const doubl
     if (const int rc = treeFromBlock(block, size, t, left)) return rc;
     hostCastRows(t, origins, dirs, t_max, n, CastArgs{iso, tol, max_iter, max_cells, flags, 0u}, left, out_status, out_t, out_xyz, out_val, out_grad,
                  out_evals, out_cells);
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+// QueryBounds from a serialised block, on the calling thread (no device): the leaves' constants come from leafBound on the host, the
+// statements of leaf_consts_kernel
+extern "C" int hpsdf_query_bounds_block(const void* block, size_t size, const double* boxes, size_t n, uint32_t subdiv, uint32_t max_leaves,
+                                        double* out_lo, double* out_hi, uint8_t* out_status, uint32_t* out_leaves) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (const int rc = boundsArgumentError(subdiv, max_leaves, n, boxes, out_lo, out_hi, out_status)) return rc;
+    HostTree ht;
+    if (const int rc = parseBlock(block, size, &ht)) return rc;
+    hostBoundsRows(ht.view, boxes, nullptr, n, subdiv, max_leaves, out_lo, out_hi, out_status, out_leaves);
+    return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+extern "C" int hpsdf_query_bounds_grid_block(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3],
+                                             uint32_t subdiv, uint32_t max_leaves, double* out_lo, double* out_hi, uint8_t* out_status,
+                                             uint32_t* out_leaves) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (!lo || !hi || !n) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const int rc = boundsArgumentError(subdiv, max_leaves, 1, lo, out_lo, out_hi, out_status)) return rc;
+    HostTree ht;
+    if (const int rc = parseBlock(block, size, &ht)) return rc;
+    BoxGrid g{};
+    size_t count = 0;
+    if (const int rc = checkBoundsGrid("hpsdf_query_bounds_grid_block", ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, &g, &count)) return rc;
+    hostBoundsRows(ht.view, nullptr, &g, count, subdiv, max_leaves, out_lo, out_hi, out_status, out_leaves);
     return HPSDF_OK;
     HPSDF_CATCH
 }

@@ -69,6 +69,13 @@ struct CastArgs;  // ray_cast.hpp
 hipError_t launchCastRays(hipStream_t stream, const TreeDev& t, const DeviceTables* dTables, const double* dOrigins, const double* dDirs,
                           const double* dTMax, size_t n, const CastArgs& a, uint8_t* dOutStatus, double* dOutT, double* dOutXyz, double* dOutVal,
                           double* dOutGrad, uint16_t* dOutEvals, uint16_t* dOutCells);
+// ---- QueryBounds (query_bounds.hip): a guaranteed range of Query over each box; dBoxes (six doubles a box), or the cells of *grid when it
+// is null; t.consts: the tree's cached constants (hpsdf_tree::boundConsts); dLeaves may be null
+struct ClsTree;  // tree_bound.hpp
+struct BoxGrid;
+hipError_t launchQueryBounds(hipStream_t stream, const ClsTree& t, int maxDegree, const DeviceTables* dTables, const double* dBoxes,
+                             const BoxGrid* grid, size_t n, uint32_t subdiv, uint32_t maxLeaves, double* dLo, double* dHi, uint8_t* dStatus,
+                             uint32_t* dLeaves);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

@@ -148,6 +148,16 @@ struct hpsdf_tree {
     mutable std::atomic<bool> hostReady{false};
     uint64_t paddedCount = 0;
     int hostCopies() const;  // HPSDF_OK, or the status of the failed download
+    // QueryBounds (query_bounds.hip): the leaves' constants G_x, G_y, G_z, S (include/hpsdf.h), 4 doubles a node.  They depend on the tree
+    // alone: the first bounds call builds them on the device under boundLock, the tree keeps them until hpsdf_tree_destroy frees them, and
+    // every later call is a launch.  hBoundConsts: their download, made by the first bounds call answered on the calling thread.
+    mutable std::mutex boundLock;
+    mutable double* dBoundConsts = nullptr;
+    mutable std::atomic<bool> boundReady{false};
+    mutable std::vector<double> hBoundConsts;
+    mutable std::atomic<bool> boundHostReady{false};
+    int boundConsts(hpsdf_ctx* ctx) const;      // HPSDF_OK, or the status of the failed build
+    int boundHostCopies(hpsdf_ctx* ctx) const;  // boundConsts, then the download
 };
 
 enum HostFieldKind { kHostAnalytic = 0, kHostCallback = 1, kHostMesh = 2, kHostTreeCsg = 3 };

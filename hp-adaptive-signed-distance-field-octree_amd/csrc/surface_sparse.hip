@@ -2,8 +2,8 @@
 // rule out (include/hpsdf.h states the blocks, the classes, the bound and the derivation of its slack).  What must equal the dense
 // call's -- case table, vertex arithmetic, wave helpers, argument checks -- is surface_common.hpp's, included by both.
 //
-//   1. sparse_depth_kernel / sparse_consts_kernel: per leaf G_x, G_y, G_z, S (leafBound) -- the depth of a node is not in the 8-byte
-//      mirror, one workgroup hands it down level by level;
+//   1. leaf_depth_kernel / leaf_consts_kernel (tree_bound.hpp, shared with QueryBounds): per leaf G_x, G_y, G_z, S (leafBound) -- the
+//      depth of a node is not in the 8-byte mirror, one workgroup hands it down level by level;
 //   2. sparse_classify_kernel: one lane per block walks the tree with the block's two extreme lattice points (classifyBlock: the very
 //      function hpsdf_surface_classify_host runs on the calling thread, so both give the same bytes);
 //   3. rocPRIM reduce + select: the class-0 blocks in block order;
@@ -34,6 +34,7 @@
 #include "leaf_eval.hpp"
 #include "surface_common.hpp"
 #include "tables.hpp"
+#include "tree_bound.hpp"
 
 namespace hpsdf {
 
@@ -45,8 +46,6 @@ constexpr uint32_t kBlockPts = kP * kP * kP;  // 729
 constexpr uint32_t kBlockCubes = kB * kB * kB;
 constexpr uint32_t kEdgeRounds = (3 * kBlockPts + kSurfThreads - 1) / kSurfThreads;  // 9
 constexpr uint32_t kCubeRounds = kBlockCubes / kSurfThreads;                     // 2
-constexpr int kLevels = HPSDF_TREE_MAX_DEPTH + 2;
-constexpr double kClip = 1.0 + 1.0 / 16384.0;  // 1 + E, E = 2^-14 (include/hpsdf.h)
 
 struct SparseLattice {
     double lo[3], h[3];
@@ -54,43 +53,6 @@ struct SparseLattice {
     uint64_t np[3];  // points per axis
     uint64_t nBlocks;
 };
-
-// What the walk reads of a tree: the 8-byte records, the line-aligned coefficients, 4 constants per node, the root map.
-struct ClsTree {
-    const NodeRec* nodes;
-    const double* coeffs;
-    const double* consts;  // per node: G_x, G_y, G_z, S (zeros for interior nodes)
-    double rootCentre[3], rootInvSizes[3];
-};
-
-// G_a and S of one leaf (include/hpsdf.h): sums of non-negative terms, in row order
-__host__ __device__ inline void leafBound(const double* __restrict__ c, uint32_t count, int depth, const double* __restrict__ nl,
-                                          const uint8_t (*__restrict__ bidx)[4], double* __restrict__ out) {
-    double g0 = 0.0, g1 = 0.0, g2 = 0.0, s = 0.0;
-    for (uint32_t r = 0; r < count; ++r) {
-        const uint32_t k0 = bidx[r][0], k1 = bidx[r][1], k2 = bidx[r][2];
-        double w = fabs(c[r]);
-        w = w * nl[k0 * 11 + depth];
-        w = w * nl[k1 * 11 + depth];
-        w = w * nl[k2 * 11 + depth];
-        s = s + w;
-        g0 = g0 + w * (double)(k0 * (k0 + 1u) / 2u);
-        g1 = g1 + w * (double)(k1 * (k1 + 1u) / 2u);
-        g2 = g2 + w * (double)(k2 * (k2 + 1u) / 2u);
-    }
-    out[0] = g0, out[1] = g1, out[2] = g2, out[3] = s;
-}
-
-// children a walk with the range [pl, ph] must visit below a node centred at c: per axis the lower half if pl < c, the upper if ph >= c
-__host__ __device__ inline uint32_t childMask(const double (&pl)[3], const double (&ph)[3], const double* c) {
-    uint32_t m = 0xFFu;
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t upper = a == 0 ? 0xAAu : (a == 1 ? 0xCCu : 0xF0u);  // children whose bit a is set
-        if (!(pl[a] < c[a])) m &= upper;
-        if (!(ph[a] >= c[a])) m &= ~upper;
-    }
-    return m;
-}
 
 // The class of block b (include/hpsdf.h).  eval(c, degree, ux, uy, uz, depth): the leaf's polynomial as Query evaluates it.
 template <class Eval>
@@ -168,68 +130,7 @@ __host__ __device__ inline uint8_t classifyBlock(const ClsTree& t, const SparseL
     return sign == 0 ? 0 : (sign > 0 ? 1 : 2);
 }
 
-struct DevEval {
-    const double* sNl;
-    const double* sRec;
-    __device__ double operator()(const double* c, int degree, double ux, double uy, double uz, int depth) const {
-        return evalLeaf<12>(c, degree, ux, uy, uz, depth, sNl, sRec);
-    }
-};
-
-// hostQueryPoint's statements (host_query.cpp): FApprox, Octree.cpp:859-901
-struct HostEval {
-    const Tables* T;
-    double operator()(const double* c, int degree, double ux, double uy, double uz, int depth) const {
-        const double u[3] = {ux, uy, uz};
-        double tab[3][13];
-        for (int a = 0; a < 3; ++a) {
-            tab[a][0] = T->normalisedLengths[0][depth];
-            double m2 = 0.0, m1 = 1.0;
-            for (int j = 1; j <= degree; ++j) {
-                const double l = T->recurrence[j][0] * u[a] * m1 - T->recurrence[j][1] * m2;
-                m2 = m1, m1 = l;
-                tab[a][j] = l * T->normalisedLengths[j][depth];
-            }
-        }
-        double f = 0.0;
-        const int n = (int)T->coeffCount[degree];
-        for (int i = 0; i < n; ++i) {
-            double lp = tab[0][T->basisIndex[i][0]];
-            lp = lp * tab[1][T->basisIndex[i][1]];
-            lp = lp * tab[2][T->basisIndex[i][2]];
-            f = f + c[i] * lp;
-        }
-        return f;
-    }
-};
-
 // ---- constants and classes -----------------------------------------------------------------------------------------------------
-
-// depth[i] of every node, handed down from the root level by level by ONE workgroup (a node's record does not hold it)
-__global__ __launch_bounds__(1024) void sparse_depth_kernel(const NodeRec* __restrict__ nodes, uint32_t nNodes, int maxDepth, uint8_t* depth) {
-    for (uint32_t i = threadIdx.x; i < nNodes; i += 1024u) depth[i] = i == 0 ? 0 : 0xFF;
-    __syncthreads();
-    for (int level = 0; level < maxDepth; ++level) {
-        for (uint32_t i = threadIdx.x; i < nNodes; i += 1024u) {
-            const NodeRec rec = nodes[i];
-            if (depth[i] == level && rec.b == kInteriorTag && rec.a < nNodes && nNodes - rec.a >= 8u)
-                for (uint32_t c = 0; c < 8u; ++c) depth[rec.a + c] = (uint8_t)(level + 1);
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kSurfThreads) void sparse_consts_kernel(const NodeRec* __restrict__ nodes, const double* __restrict__ coeffs,
-                                                                 const uint8_t* __restrict__ depth, uint32_t nNodes,
-                                                                 const DeviceTables* __restrict__ T, double* __restrict__ consts) {
-    const uint32_t i = blockIdx.x * kSurfThreads + threadIdx.x;
-    if (i >= nNodes) return;
-    double out[4] = {0.0, 0.0, 0.0, 0.0};
-    const NodeRec rec = nodes[i];
-    const int d = depth[i];
-    if (rec.b <= 12u && d <= HPSDF_TREE_MAX_DEPTH) leafBound(coeffs + rec.a, T->count[rec.b], d, &T->nl[0][0], T->bidx, out);
-    for (int k = 0; k < 4; ++k) consts[4 * (size_t)i + k] = out[k];
-}
 
 __global__ __launch_bounds__(kSurfThreads) void sparse_classify_kernel(ClsTree t, const DeviceTables* __restrict__ T, SparseLattice g, double iso,
                                                                    uint64_t firstBlock, uint64_t count, uint8_t* __restrict__ out,
@@ -238,7 +139,7 @@ __global__ __launch_bounds__(kSurfThreads) void sparse_classify_kernel(ClsTree t
     __shared__ double sRec[26];
     stageQueryTables(T, sNl, sRec);
     __syncthreads();
-    const DevEval eval{sNl, sRec};
+    const DevEval<12> eval{sNl, sRec};
     unsigned long long mine = 0;
     const uint64_t stride = (uint64_t)gridDim.x * kSurfThreads;
     for (uint64_t i = (uint64_t)blockIdx.x * kSurfThreads + threadIdx.x; i < count; i += stride) {
@@ -463,11 +364,7 @@ int classifyOnDevice(hpsdf_ctx* ctx, const hpsdf_tree* t, DevPool& pool, const S
     double* dConsts = nullptr;
     SURF_ALLOC(pool, dDepth, (size_t)nNodes, "node depths");
     SURF_ALLOC(pool, dConsts, (size_t)nNodes * 4 * sizeof(double), "leaf constants");
-    hipLaunchKernelGGL(sparse_depth_kernel, dim3(1), dim3(1024), 0, s, t->dev.nodes, nNodes, t->maxDepth, dDepth);
-    HPSDF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sparse_consts_kernel, dim3(gridOf(nNodes, 1u << 24)), dim3(kSurfThreads), 0, s, t->dev.nodes, t->dev.coeffs, dDepth, nNodes,
-                       ctx->dTables, dConsts);
-    HPSDF_HIP(hipGetLastError());
+    HPSDF_HIP(launchLeafConsts(s, t, ctx->dTables, dDepth, dConsts));
     ClsTree ct{};
     ct.nodes = t->dev.nodes, ct.coeffs = t->dev.coeffs, ct.consts = dConsts;
     for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
@@ -634,40 +531,6 @@ int extractSparse(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* lo, const d
     }
     st.peak_scratch_bytes = pool.peak;
     if (stats) *stats = st;
-    return HPSDF_OK;
-}
-
-// a serialised block -> the arrays the walk reads: the query mirror (block.hpp) and the constants
-struct HostTree {
-    BlockMirror m;
-    std::vector<double> consts;
-    ClsTree view{};
-};
-
-int parseBlock(const void* block, size_t size, HostTree* out) {
-    BlockView v;
-    BlockMirror& m = out->m;
-    const Tables& T = tables();
-    {
-        std::string why;
-        int rc = readBlock(block, size, v, why);
-        if (!rc) rc = mirrorBlock(v, T, m, why);
-        if (rc) return fail(rc, why);
-    }
-    uint8_t bidx[kMaxCoeffs][4];
-    for (int i = 0; i < kMaxCoeffs; ++i)
-        for (int k = 0; k < 3; ++k) bidx[i][k] = (uint8_t)T.basisIndex[i][k];
-    out->consts.assign(4 * (size_t)v.nNodes, 0.0);
-    for (const uint64_t i : m.walk.order) {
-        const NodeRec rec = m.recs[i];
-        if (rec.b <= 12u && m.walk.depthOf[i] <= HPSDF_TREE_MAX_DEPTH)
-            leafBound(m.padded.data() + rec.a, (uint32_t)T.coeffCount[rec.b], m.walk.depthOf[i], &T.normalisedLengths[0][0], bidx,
-                      out->consts.data() + 4 * i);
-    }
-    out->view.nodes = m.recs.data();
-    out->view.coeffs = m.padded.data();
-    out->view.consts = out->consts.data();
-    for (int a = 0; a < 3; ++a) out->view.rootCentre[a] = m.rootCentre[a], out->view.rootInvSizes[a] = m.rootInvSizes[a];
     return HPSDF_OK;
 }
 

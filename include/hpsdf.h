@@ -621,6 +621,97 @@ HPSDF_API int hpsdf_surface_classify_host(const void* block, size_t size, const 
 HPSDF_API int hpsdf_surface_classify_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3],
                                             const uint32_t n[3], double iso, uint64_t first_block, uint64_t count, uint8_t* out);
 
+/* ---- QueryBounds: a guaranteed range of Query over axis-aligned boxes (no reference counterpart) ---------------------------------------
+ * One row per box: six doubles, the lower corner a[3] then the upper corner b[3], world coordinates.  The result is an interval
+ * [lo, hi] with this guarantee: for every point x with a <= x <= b componentwise, Query(x) -- the double this library computes at x,
+ * not the polynomial's exact value -- satisfies lo <= Query(x) <= hi.  A sampled minimum proves nothing about a region; this does,
+ * because a leaf is a polynomial whose variation over a box is bounded by its coefficients.  The rule is the block classification's
+ * (hpsdf_extract_surface_sparse above: G_a, S, E, the child selection, HPSDF_SURFACE_SLACK, HPSDF_SURFACE_ETA), with the block of
+ * cubes replaced by any box and the class byte by the interval.  Host, device and block entries run the same statements
+ * (csrc/tree_bound.hpp, boundsWalk; every expression below has the association written, no multiply-add is fused) and give the same
+ * bits.  Per call: subdiv in {1, 2, 4}, max_leaves in 1..65535.
+ *   1 map      pl_a = (a_a - rootCentre_a) * rootInvSizes_a,  ph_a = (b_a - rootCentre_a) * rootInvSizes_a: Query's own expression on the
+ *              two extreme points.  If (float)pl_a or (float)ph_a is outside [-0.5, 0.5] on an axis (Query's containment test; a NaN
+ *              or infinite coordinate fails it) or !(pl_a <= ph_a):       status = HPSDF_BOUNDS_INVALID, lo = hi = quiet NaN, leaves = 0
+ *   2 walk     lo = +inf, hi = -inf, leaves = 0.  From the root, depth first, the children of a node centred at c in increasing
+ *              index, child i visited iff on every axis (bit a of i clear and pl_a < c_a) or (bit a of i set and ph_a >= c_a): Query
+ *              takes the upper child iff p_a >= c_a and p is monotone in x, so this is a superset of the leaves any point of the box
+ *              reaches.  Centres are exact dyadics.  At each leaf reached:
+ *                if leaves == max_leaves:                          status = HPSDF_BOUNDS_LEAF_LIMIT, lo = -inf, hi = +inf, stop
+ *                leaves = leaves + 1
+ *   3 bound    in that leaf (depth d, centre c, s = 2^(d+1)), per axis:  ua = (pl_a - c_a) * s,  ub = (ph_a - c_a) * s  (Query's
+ *              expression, monotone too);  if ua < -(1 + E): ua = -(1 + E);  if ub > 1 + E: ub = 1 + E  (E = 2^-14);  if !(ua <= ub)
+ *              on an axis no point of the box lies in the leaf: next leaf.  Otherwise w_a = (ub - ua) * (1.0 / subdiv), and for the
+ *              subdiv^3 sub-boxes (i, j, k), x fastest, then y, then z, per axis with its index m:
+ *                l = ua + (double)m * w_a;   h = (m + 1 == subdiv) ? ub : ua + (double)(m + 1) * w_a
+ *                u_c = 0.5 * (l + h);   rho = 0.5 * (h - l)
+ *              (h of one sub-box and l of the next are the same expression: the sub-boxes tile [ua, ub] exactly), then
+ *                f_c = the leaf's polynomial at u_c, by the leaf evaluation Query uses
+ *                e   = HPSDF_SURFACE_SLACK * ((rho_0 * G_0 + rho_1 * G_1) + rho_2 * G_2) + HPSDF_SURFACE_ETA * S
+ *                if f_c or e is not finite:                        status = HPSDF_BOUNDS_NOT_FINITE, lo = -inf, hi = +inf, stop
+ *                el = f_c - e and eh = f_c + e, each rounded TOWARDS f_c: the smallest double >= the exact f_c - e, the largest double <=
+ *                the exact f_c + e (the rounded sum, or its neighbour on f_c's side where the sum rounded away from f_c; the rounding
+ *                error of an addition is a double and is computed exactly, so this too is the same bits everywhere)
+ *                if (el < lo) lo = el;      if (eh > hi) hi = eh
+ *   4 result   status = HPSDF_BOUNDS_OK with [lo, hi] (a valid box reaches at least one leaf, so lo <= hi), leaves = the leaves passed.
+ * The infinite intervals of LEAF_LIMIT and NOT_FINITE are true statements, not errors; `leaves` then holds the count at the stop
+ * (max_leaves for LEAF_LIMIT).  subdiv = 1 bounds a leaf's part of the box as the block classification does; 2 and 4 halve and
+ * quarter rho per axis at 8 and 64 evaluations a leaf: e shrinks roughly in proportion until HPSDF_SURFACE_ETA * S, the floor of a
+ * point box, is what is left.
+ * Why it holds, and why the classification's constants still cover this use (derived, not tuned; nothing was widened).
+ *   Reach: a point x of the box has p(x) in [pl, ph] per axis (one subtraction and one multiplication by a positive number, both
+ *   monotone), so the leaf Query descends to is visited, and there its u lies in [ua, ub] before clipping and, by the containment
+ *   test, within [-(1 + E), 1 + E]: in exactly one sub-box's [l, h] up to the shared faces.
+ *   Variation: with u_c and rho exact, |f(u) - f(u_c)| <= tau^3 sum_a rho_a G_a, tau^3 < 1.0268 (the sparse section's argument; it
+ *   never used the block's shape).  subdiv only shrinks rho, which the mean value bound is linear in, and changes nothing else.
+ *   Relative roundings: G_a (455 positive terms: under 2^-43 relative), rho (one subtraction), the three products and two sums of e
+ *   and the multiplication by the slack are each a few ulps relative; 1.03125 / 1.0268 leaves 0.4 % for them, as before.
+ *   The one rounding that is NOT relative to rho: u_c = 0.5 * (l + h) is off by up to 2^-53 (half an ulp below 2), which moves the
+ *   centre by that much whatever rho is -- a box a few ulps wide has its centre on one of its ends.  The classification has the same
+ *   term (its blocks are never that thin, but nothing forbids it).  It is absolute, so it is charged to ETA: sup |df/du_a| <= tau^3
+ *   G_a and G_a <= 78 S (k (k + 1) / 2 <= 78 for k <= 12), hence at most 3 * 2^-53 * 78 * 1.0268 S < 2^-45 S over the three axes.
+ *   Evaluation: Query(x) and f_c each differ from the exact polynomial by under 2^-41 S (the sparse section): 2^-40 S for the two.
+ *   f_c -/+ e: the two ends are rounded towards f_c, which takes less than one spacing of doubles off e: under 2^-52 (|f_c| + e) <=
+ *   2^-52 (1.0268 S + e) -- 2^-51.9 S absolute plus a 2^-52 relative part of e that the 0.4 % takes.  Rounding to nearest would be as
+ *   sound; towards f_c the interval is never wider than the rule's own 2 e: hi - lo <= 2 e in exact arithmetic, for every box.
+ *   Sum charged to ETA: 2^-40 + 2^-45 + 2^-51.9 < 2^-39.9 S, against HPSDF_SURFACE_ETA = 2^-32: the 2^8 of headroom the sparse
+ *   section left is now 2^7.9.  Both constants stay as they are.
+ *   Not finite: a leaf with an infinite or NaN coefficient has S (and e) infinite or NaN and is reported as NOT_FINITE, never bounded.
+ *   A point box (a == b): every sub-box is the point, f_c is Query(a) bit for bit, e is ETA S with one rounding, and lo <= Query(a) <= hi
+ *   with hi - lo <= 2 ETA S (1 + 2^-43): the ends' rounding adds nothing to the width.
+ * Outputs per box: out_lo, out_hi (double) and out_status (uint8_t, HPSDF_BOUNDS_*) are required; out_leaves (uint32_t) is optional:
+ * when NULL it takes no slot and is left untouched.
+ * hpsdf_query_bounds_grid_*: the boxes are the cells of a lattice lo[3], hi[3], n[3] (hpsdf_extract_surface's arguments and checks:
+ * finite, lo < hi, n >= 1, both extreme points inside the root), h_a = (hi_a - lo_a) / n_a; box i + n0 (j + n1 k) is cell (i, j, k)
+ * with corners lo_a + (double)i * h_a and lo_a + (double)(i + 1) * h_a -- the surface lattice's own arithmetic, so neighbouring cells
+ * share their faces exactly; n0 n1 n2 <= 2^32.  No box array is materialised; the outputs hold n0 n1 n2 rows, x fastest, and are the
+ * box entries' bits for the same corners.
+ * A NULL tree, a required array NULL with n > 0 (grid: NULL lo, hi or n), subdiv not 1, 2 or 4, max_leaves outside 1..65535, a
+ * lattice hpsdf_extract_surface would refuse: HPSDF_ERR_INVALID_ARGUMENT, and no output is written.  n == 0 is HPSDF_OK.  _device is
+ * asynchronous on the context stream (the first bounds call on a tree builds the leaves' constants G_a, S once, under a lock, and keeps
+ * them with the tree until hpsdf_tree_destroy: 32 bytes a node; every later call only launches); _host answers calls of up to 32
+ * boxes on the calling thread and sends larger ones through the device; _block needs no device: it works from a serialised block on
+ * the calling thread and accepts and refuses blocks as hpsdf_project_block does.
+ * Not done: boxes reaching outside the root are INVALID, not clipped; a large box is one lane's walk (see max_leaves); the enclosure
+ * is first order (it does not use the gradient at the centre). */
+enum { HPSDF_BOUNDS_OK = 0, HPSDF_BOUNDS_LEAF_LIMIT = 1, HPSDF_BOUNDS_INVALID = 2, HPSDF_BOUNDS_NOT_FINITE = 3 };
+HPSDF_API int hpsdf_query_bounds_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* d_boxes, size_t n, uint32_t subdiv,
+                                        uint32_t max_leaves, double* d_out_lo, double* d_out_hi, uint8_t* d_out_status,
+                                        uint32_t* d_out_leaves);
+HPSDF_API int hpsdf_query_bounds_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double* boxes, size_t n, uint32_t subdiv, uint32_t max_leaves,
+                                      double* out_lo, double* out_hi, uint8_t* out_status, uint32_t* out_leaves);
+HPSDF_API int hpsdf_query_bounds_block(const void* block, size_t size, const double* boxes, size_t n, uint32_t subdiv, uint32_t max_leaves,
+                                       double* out_lo, double* out_hi, uint8_t* out_status, uint32_t* out_leaves);
+HPSDF_API int hpsdf_query_bounds_grid_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3],
+                                             uint32_t subdiv, uint32_t max_leaves, double* d_out_lo, double* d_out_hi, uint8_t* d_out_status,
+                                             uint32_t* d_out_leaves);
+HPSDF_API int hpsdf_query_bounds_grid_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3],
+                                           uint32_t subdiv, uint32_t max_leaves, double* out_lo, double* out_hi, uint8_t* out_status,
+                                           uint32_t* out_leaves);
+HPSDF_API int hpsdf_query_bounds_grid_block(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3],
+                                            uint32_t subdiv, uint32_t max_leaves, double* out_lo, double* out_hi, uint8_t* out_status,
+                                            uint32_t* out_leaves);
+
 /* ---- Create: Octree::Create under the canonical round schedule ---------------
  * (Octree.cpp:312-352, 194-309, 558-659, 804-856, 1007-1093; schedule: DESIGN.md)
  *

@@ -661,6 +661,43 @@ class Octree {
                                    outXyz, outVal, outGrad, outEvals, outCells));
     }
 
+    /// An interval [lo_, hi_] that holds Query(x) for EVERY point x of box_ (no reference counterpart; include/hpsdf.h, "QueryBounds"):
+    /// lo_ > 0 proves the box outside the surface, hi_ < 0 inside it -- what no sampling of Query can.  subdiv_ (1, 2 or 4) splits a
+    /// leaf's part of the box that many times per axis: tighter, at 8 or 64 evaluations a leaf.  Returns the status: HPSDF_BOUNDS_OK;
+    /// _LEAF_LIMIT (more than maxLeaves_ leaves: [-inf, inf]); _INVALID (a corner outside the root, a NaN, min > max: NaNs);
+    /// _NOT_FINITE (a leaf with a non-finite coefficient: [-inf, inf]).  leaves_ (optional): the leaves the walk passed
+    int QueryBounds(const Eigen::AlignedBox3d& box_, f64& lo_, f64& hi_, uint32_t subdiv_ = 1, uint32_t maxLeaves_ = 4096,
+                    uint32_t* leaves_ = nullptr) const {
+        const double b[6] = {box_.min()(0), box_.min()(1), box_.min()(2), box_.max()(0), box_.max()(1), box_.max()(2)};
+        double lo = 0.0, hi = 0.0;
+        uint8_t st = 0;
+        QueryBounds(b, 1, &lo, &hi, &st, leaves_, subdiv_, maxLeaves_);
+        lo_ = lo, hi_ = hi;
+        return st;
+    }
+    /// Batched form over host arrays: six doubles a box (min, then max); outLeaves may be null
+    void QueryBounds(const double* boxes, usize n, double* outLo, double* outHi, uint8_t* outStatus, uint32_t* outLeaves = nullptr,
+                     uint32_t subdiv_ = 1, uint32_t maxLeaves_ = 4096) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        check(hpsdf_query_bounds_host(ctx_, t, boxes, n, subdiv_, maxLeaves_, outLo, outHi, outStatus, outLeaves));
+    }
+    /// The same over the cells of ExtractSurface's lattice (resolution_[a] cells per axis of area_; no box array is made): the outputs
+    /// hold resolution_[0] * resolution_[1] * resolution_[2] rows, x fastest
+    void QueryBoundsGrid(const Eigen::AlignedBox3f& area_, const Eigen::Vector3i& resolution_, double* outLo, double* outHi, uint8_t* outStatus,
+                         uint32_t* outLeaves = nullptr, uint32_t subdiv_ = 1, uint32_t maxLeaves_ = 4096) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        const double lo[3] = {area_.min()(0), area_.min()(1), area_.min()(2)};
+        const double hi[3] = {area_.max()(0), area_.max()(1), area_.max()(2)};
+        uint32_t n[3];
+        for (int a = 0; a < 3; ++a) {
+            if (resolution_(a) < 1) throw Error(HPSDF_ERR_INVALID_ARGUMENT, "resolution must be at least 1 per axis");
+            n[a] = (uint32_t)resolution_(a);
+        }
+        check(hpsdf_query_bounds_grid_host(ctx_, t, lo, hi, n, subdiv_, maxLeaves_, outLo, outHi, outStatus, outLeaves));
+    }
+
     /// Returns the aabb of the root node   (Octree.h:81)
     Eigen::AlignedBox3f GetRootAABB() const { return config_.root; }
 
