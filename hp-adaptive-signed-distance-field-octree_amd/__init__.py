@@ -190,6 +190,9 @@ _SIGNATURES = {
                                                C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_query_bounds_grid_block": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_integrate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_integrate_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -760,6 +763,14 @@ class DeviceTree:
         check(lib().hpsdf_query_bounds_grid_device(self.ctx.handle, self.handle, lo3, hi3, n3, _max_iter(subdiv), _max_iter(max_leaves),
                                                    vp(d_out_lo_ptr), vp(d_out_hi_ptr), vp(d_out_status_ptr), vp(d_out_leaves_ptr)))
 
+    def integrate(self, iso=0.0, depth=8, samples=2, max_cells=1 << 24, cells=False, host=False):
+        """Integrate (include/hpsdf.h): a guaranteed enclosure of the volume of {Query < iso} over the root and an estimate of its zeroth,
+        first and second moments, by refining the leaves into dyadic cells down to absolute depth `depth` where the leaves' bound cannot
+        decide the sign -> Integral (the struct's fields, centroid, inertia, and with cells=True the final cells as a structured array
+        of CELL_DTYPE).  host=True computes on the calling thread from the tree's host copies: the same bytes."""
+        fn = lib().hpsdf_integrate_host if host else lib().hpsdf_integrate_device
+        return _integrate(lambda *rest: fn(self.ctx.handle, self.handle, *rest), iso, depth, samples, max_cells, cells)
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1217,6 +1228,13 @@ class Octree:
         n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
         return self._tree.query_bounds_grid(view_min, view_max, n3, subdiv, max_leaves)
 
+    def Integrate(self, iso=0.0, depth=8, samples=2, max_cells=1 << 24, cells=False):
+        """Volume bounds and moments of the solid {Query < iso} (DeviceTree.integrate) -> Integral: volume_lo <= volume <= volume_hi
+        guaranteed, volume / m1 / m2 estimated, centroid and inertia derived."""
+        if self._tree is None:
+            raise HpsdfError(6, "Query on an empty octree")
+        return self._tree.integrate(iso, depth, samples, max_cells, cells)
+
     def QueryRay(self, origins, directions, t_max):
         """Octree::QueryRay (Octree.h:75) for one ray -> (hit, t) or (n,3) arrays -> (hit[n], t[n])."""
         if self._tree is None:
@@ -1394,6 +1412,76 @@ def query_bounds_grid_block(block, lo, hi, n, subdiv=1, max_leaves=4096):
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     check(lib().hpsdf_query_bounds_grid_block(buf, len(buf), lo3, hi3, n3, _max_iter(subdiv), _max_iter(max_leaves), *[vp(x) for x in bufs]))
     return bufs
+
+
+INTEGRATE_OK, INTEGRATE_CELL_LIMIT, INTEGRATE_NOT_FINITE = 0, 1, 2  # HPSDF_INTEGRATE_*: Integral.status
+CELL_DTYPE = np.dtype([("node", "<u4"), ("depth", "u1"), ("cls", "u1"), ("i", "<u2"), ("j", "<u2"), ("k", "<u2")])  # hpsdf_integrate_cell
+
+
+class hpsdf_integral(C.Structure):
+    _fields_ = [("unit_volume_lo", C.c_double), ("unit_volume_hi", C.c_double), ("unit_volume", C.c_double),
+                ("volume_lo", C.c_double), ("volume_hi", C.c_double), ("volume", C.c_double),
+                ("m1", C.c_double * 3), ("m2", C.c_double * 6), ("unit_m1", C.c_double * 3), ("unit_m2", C.c_double * 6),
+                ("cells_inside", C.c_uint64), ("cells_outside", C.c_uint64), ("cells_undecided", C.c_uint64), ("evaluations", C.c_uint64),
+                ("status", C.c_uint32), ("levels", C.c_uint32)]
+
+
+class Integral:
+    """hpsdf_integral's fields (arrays as numpy), `raw` (the struct's bytes), `cells` (a CELL_DTYPE array, or None when not asked for),
+    and derived: centroid = m1 / volume; inertia: the 3 x 3 inertia tensor about the centroid at unit density,
+    trace(C) I - C with C_jk = m2_jk - volume centroid_j centroid_k."""
+
+    def __init__(self, st, cells):
+        self.raw = bytes(st)
+        for name, _ in st._fields_:
+            v = getattr(st, name)
+            setattr(self, name, np.array(v[:]) if hasattr(v, "__len__") else v)
+        self.cells = cells
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.centroid = self.m1 / self.volume
+            xx, yy, zz, xy, xz, yz = self.m2
+            second = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) - self.volume * np.outer(self.centroid, self.centroid)
+            self.inertia = np.trace(second) * np.eye(3) - second
+
+    def __repr__(self):
+        return "Integral(status=%d, levels=%d, volume in [%r, %r], estimate %r)" % (self.status, self.levels, self.volume_lo, self.volume_hi, self.volume)
+
+
+def _integrate(call, iso, depth, samples, max_cells, cells):
+    """call(iso, depth, samples, max_cells, out, out_cells, out_n_cells) -> Integral; the malloc'd cell array copied and freed."""
+    st = hpsdf_integral()
+    ptr, count = C.c_void_p(), C.c_uint64()
+    check(call(float(iso), _max_iter(depth), _max_iter(samples), _max_iter(max_cells), C.byref(st),
+               C.byref(ptr) if cells else None, C.byref(count) if cells else None))
+    arr = None
+    if cells:
+        arr = np.zeros(count.value, CELL_DTYPE)
+        if count.value:
+            C.memmove(arr.ctypes.data, ptr, count.value * CELL_DTYPE.itemsize)
+        lib()._libc.free(ptr)
+    return Integral(st, arr)
+
+
+def integrate_block(block, iso=0.0, depth=8, samples=2, max_cells=1 << 24, cells=False):
+    """hpsdf_integrate_block: DeviceTree.integrate's result from a serialised block on the calling thread (no device)."""
+    buf = bytes(block)
+    return _integrate(lambda *rest: lib().hpsdf_integrate_block(buf, len(buf), *rest), iso, depth, samples, max_cells, cells)
+
+
+def cells_to_boxes(block_or_tree, cells):
+    """The world boxes of Integrate's cells -> f64 [n, 6], QueryBounds' row format (lower corner, upper corner): per axis
+    rootCentre + p * size with p = -0.5 + i * 2^-depth and -0.5 + (i + 1) * 2^-depth (exact), size = 1 / rootInvSizes.
+    block_or_tree: a serialised block, or a DeviceTree or an Octree (the block it keeps)."""
+    raw = bytes(block_or_tree) if isinstance(block_or_tree, (bytes, bytearray, memoryview)) else bytes(block_or_tree.block)
+    cfg = PodConfig.from_buffer_copy(raw[-C.sizeof(PodConfig):])
+    rmin, rmax = np.array(cfg.root_min[:], np.float32), np.array(cfg.root_max[:], np.float32)
+    centre = ((rmin + rmax) / np.float32(2.0)).astype(np.float64)
+    size = 1.0 / (np.float32(1.0) / (rmax - rmin)).astype(np.float64)
+    s = 1.0 / (1 << cells["depth"].astype(np.int64)).astype(np.float64)
+    ijk = np.stack([cells["i"], cells["j"], cells["k"]], 1).astype(np.float64)
+    lo = -0.5 + ijk * s[:, None]
+    hi = lo + s[:, None]
+    return np.ascontiguousarray(np.concatenate([centre + lo * size, centre + hi * size], 1))
 
 
 def query_hessian_block(block, pts, unit=False, curvature=False):

@@ -21,6 +21,7 @@
 #include "frontier.hpp"
 #include "block.hpp"
 #include "host_call.hpp"
+#include "integrate.hpp"
 #include "launch.hpp"
 #include "ray_cast.hpp"
 #include "runtime.hpp"
@@ -833,6 +834,7 @@ int hpsdf_tree_destroy(hpsdf_tree* t) {
     if (t->dTopRec) (void)hipFree(t->dTopRec);
     if (t->dCoeffs) (void)hipFree(t->dCoeffs);
     if (t->dBoundConsts) (void)hipFree(t->dBoundConsts);
+    if (t->dLeafCells) (void)hipFree(t->dLeafCells);
     delete t;
     return HPSDF_OK;
 }
@@ -1176,6 +1178,39 @@ int hpsdf_query_bounds_grid_host(hpsdf_ctx* ctx, const hpsdf_tree* t, const doub
     size_t count = 0;
     if (const int rc = checkBoundsGrid("hpsdf_query_bounds_grid_host", t->dev.rootCentre, t->dev.rootInvSizes, lo, hi, n, &g, &count)) return rc;
     return boundsOnHost(ctx, t, nullptr, &g, count, subdiv, maxLeaves, outLo, outHi, outStatus, outLeaves);
+    HPSDF_CATCH
+}
+
+// Integrate (include/hpsdf.h): volume bounds and moments of the solid (integrate.hip, integrate.hpp, host_query.cpp)
+int hpsdf_integrate_device(hpsdf_ctx* ctx, const hpsdf_tree* t, double iso, uint32_t depth, uint32_t samples, uint32_t maxCells, hpsdf_integral* out,
+                           hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = integrateArgumentError(iso, depth, samples, maxCells, out, outCells, outCount)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (const int rc = treeOnContext(ctx, t)) return rc;
+    if (const int rc = t->boundConsts(ctx)) return rc;
+    if (const int rc = t->integrateLeaves(ctx)) return rc;
+    ClsTree ct{t->dev.nodes, t->dev.coeffs, t->dBoundConsts, {}, {}};
+    for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
+    const IntegrateArgs a{iso, depth, samples, maxCells};
+    return integrateOnDevice(ctx, ct, t->maxDegree, t->dLeafCells, t->nLeafCells, a, out, outCells, outCount);
+    HPSDF_CATCH
+}
+
+int hpsdf_integrate_host(hpsdf_ctx* ctx, const hpsdf_tree* t, double iso, uint32_t depth, uint32_t samples, uint32_t maxCells, hpsdf_integral* out,
+                         hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = integrateArgumentError(iso, depth, samples, maxCells, out, outCells, outCount)) return rc;
+    if (!t) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (t->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    if (const int hc = t->hostCopies()) return hc;
+    if (const int hc = t->boundHostCopies(ctx)) return hc;
+    ClsTree ct{t->hRecs.data(), t->hPadded.data(), t->hBoundConsts.data(), {}, {}};
+    for (int a = 0; a < 3; ++a) ct.rootCentre[a] = t->dev.rootCentre[a], ct.rootInvSizes[a] = t->dev.rootInvSizes[a];
+    const IntegrateArgs a{iso, depth, samples, maxCells};
+    return hostIntegrate(ct, t->hRecs.size(), a, out, outCells, outCount);
     HPSDF_CATCH
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "block.hpp"
+#include "integrate.hpp"
 #include "leaf_gradient.hpp"
 #include "leaf_hessian.hpp"
 #include "ray_cast.hpp"
@@ -410,6 +411,80 @@ int boundsArgumentError(uint32_t subdiv, uint32_t maxLeaves, size_t n, const voi
     return HPSDF_OK;
 }
 
+// Integrate (include/hpsdf.h) on the calling thread: integrateLevels (integrate.hpp) over two host lists, with Query's leaf evaluation --
+// the statements of the kernels of integrate.hip, the rows reduced by the same rule.
+namespace {
+
+struct HostIntegrateLists {
+    const ClsTree& t;
+    const IntegrateArgs& a;
+    HostEval eval;
+    std::vector<IntegrateCell> cur, next;
+    std::vector<uint8_t> split;
+    std::vector<double> rows;
+
+    int classify(int level, uint32_t n, uint32_t* nSplit, bool* finite) {
+        split.assign(n, 0);
+        uint32_t count = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            bool ok = true;
+            IntegrateCell& c = cur[i];
+            c.cls = (uint8_t)integrateCellClass(t, c, level, a.iso, eval, &ok);
+            if (!ok) *finite = false;
+            split[i] = c.cls == 0u && c.depth < a.depth;
+            count += split[i];
+        }
+        *nSplit = count;
+        return HPSDF_OK;
+    }
+
+    int contribute(int level, uint32_t n, uint32_t nSplit, std::vector<IntegrateCell>* cells, double (&T)[kIntRow]) {
+        next.clear();
+        next.reserve(8 * (size_t)nSplit);
+        rows.clear();
+        double x[kIntBlock][kIntRow];
+        for (uint32_t b = 0; b < n; b += kIntBlock) {
+            std::memset(x, 0, sizeof x);
+            for (uint32_t i = b; i < n && i < b + kIntBlock; ++i) {
+                const IntegrateCell& c = cur[i];
+                if (nSplit != 0 && split[i]) {
+                    for (uint32_t ch = 0; ch < 8u; ++ch) next.push_back(integrateChild(c, ch));
+                    continue;
+                }
+                integrateCellRow(t, c, level, a.iso, a.samples, eval, x[i - b]);
+                if (cells) cells->push_back(c);
+            }
+            integrateBlockTree(x);
+            rows.insert(rows.end(), x[0], x[0] + kIntRow);
+        }
+        integrateReduceRows(rows, T);
+        cur.swap(next);
+        return HPSDF_OK;
+    }
+};
+
+}  // namespace
+
+int hostIntegrate(const ClsTree& t, size_t nNodes, const IntegrateArgs& a, hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HostIntegrateLists L{t, a, HostEval{&tables()}, {}, {}, {}, {}};
+    integrateLeafCells(t.nodes, nNodes, L.cur);
+    IntegrateSums S;
+    if (const int rc = integrateLevels(L, a, (uint32_t)L.cur.size(), outCells != nullptr, S)) return rc;
+    hpsdf_integral r;
+    integrateResult(S, t.rootCentre, t.rootInvSizes, a.samples, &r);
+    return integrateHandOver(S, r, out, outCells, outCount);
+}
+
+// what hpsdf_integrate_* reject before anything runs (0: fine)
+int integrateArgumentError(double iso, uint32_t depth, uint32_t samples, uint32_t maxCells, const void* out, const void* outCells, const void* outCount) {
+    if (!(std::fabs(iso) <= DBL_MAX)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_integrate: iso must be finite");
+    if (depth > 15u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_integrate: depth must be in 0..15");
+    if (samples != 1u && samples != 2u && samples != 4u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_integrate: samples must be 1, 2 or 4");
+    if (maxCells < 8u || maxCells > (1u << 28)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_integrate: max_cells must be in 8..2^28");
+    if (!out || (outCells != nullptr) != (outCount != nullptr)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    return HPSDF_OK;
+}
+
 namespace {
 
 // What the *_block entries answer from: a serialised block as a host-only tree handle -- validated and laid out like the device mirror
@@ -523,5 +598,19 @@ extern "C" int hpsdf_query_bounds_grid_block(const void* block, size_t size, con
     if (const int rc = checkBoundsGrid("hpsdf_query_bounds_grid_block", ht.view.rootCentre, ht.view.rootInvSizes, lo, hi, n, &g, &count)) return rc;
     hostBoundsRows(ht.view, nullptr, &g, count, subdiv, max_leaves, out_lo, out_hi, out_status, out_leaves);
     return HPSDF_OK;
+    HPSDF_CATCH
+}
+
+// Integrate from a serialised block, on the calling thread (no device): list 0 from the mirror's records, the leaves' constants from
+// leafBound on the host
+extern "C" int hpsdf_integrate_block(const void* block, size_t size, double iso, uint32_t depth, uint32_t samples, uint32_t max_cells,
+                                     hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (const int rc = integrateArgumentError(iso, depth, samples, max_cells, out, out_cells, out_n_cells)) return rc;
+    HostTree ht;
+    if (const int rc = parseBlock(block, size, &ht)) return rc;
+    const IntegrateArgs a{iso, depth, samples, max_cells};
+    return hostIntegrate(ht.view, ht.m.recs.size(), a, out, out_cells, out_n_cells);
     HPSDF_CATCH
 }

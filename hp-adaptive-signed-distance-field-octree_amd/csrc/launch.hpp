@@ -76,6 +76,12 @@ struct BoxGrid;
 hipError_t launchQueryBounds(hipStream_t stream, const ClsTree& t, int maxDegree, const DeviceTables* dTables, const double* dBoxes,
                              const BoxGrid* grid, size_t n, uint32_t subdiv, uint32_t maxLeaves, double* dLo, double* dHi, uint8_t* dStatus,
                              uint32_t* dLeaves);
+// ---- Integrate (integrate.hip): volume bounds and moments of {Query < iso} over the root; t.consts: the tree's cached constants, dLeaves:
+// its cached list 0 (hpsdf_tree::integrateLeaves).  Synchronises the stream; outCells / outCount may both be null
+struct IntegrateCell;  // integrate.hpp
+struct IntegrateArgs;
+int integrateOnDevice(hpsdf_ctx* ctx, const ClsTree& t, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves, const IntegrateArgs& a,
+                      hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

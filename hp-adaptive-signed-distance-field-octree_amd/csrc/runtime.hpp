@@ -75,6 +75,10 @@ struct Workspace {
 
 }  // namespace hpsdf
 
+namespace hpsdf {
+struct IntegrateCell;  // integrate.hpp
+}
+
 struct hpsdf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -158,6 +162,12 @@ struct hpsdf_tree {
     mutable std::atomic<bool> boundHostReady{false};
     int boundConsts(hpsdf_ctx* ctx) const;      // HPSDF_OK, or the status of the failed build
     int boundHostCopies(hpsdf_ctx* ctx) const;  // boundConsts, then the download
+    // Integrate (integrate.hip): list 0 -- the leaves in increasing node index with their depth and integer coordinates, 12 bytes a leaf --
+    // made by the first Integrate call on the tree, under boundLock, and kept until hpsdf_tree_destroy
+    mutable hpsdf::IntegrateCell* dLeafCells = nullptr;
+    mutable uint32_t nLeafCells = 0;
+    mutable std::atomic<bool> leafCellsReady{false};
+    int integrateLeaves(hpsdf_ctx* ctx) const;  // HPSDF_OK, or the status of the failed build
 };
 
 enum HostFieldKind { kHostAnalytic = 0, kHostCallback = 1, kHostMesh = 2, kHostTreeCsg = 3 };

@@ -712,6 +712,108 @@ HPSDF_API int hpsdf_query_bounds_grid_block(const void* block, size_t size, cons
                                             uint32_t subdiv, uint32_t max_leaves, double* out_lo, double* out_hi, uint8_t* out_status,
                                             uint32_t* out_leaves);
 
+/* ---- Integrate: volume bounds and moments of the solid {x in root : Query(x) < iso} (no reference counterpart) --------------------------
+ * The integral counterpart of QueryBounds: the leaves of the tree are refined level by level into dyadic cells, a cell's sign is decided
+ * by QueryBounds' rule at ONE evaluation of its leaf's polynomial, and only the cells the rule cannot decide -- those the surface passes
+ * through -- are split.  The work grows with the surface's area (4^depth), not with the root's volume (8^depth).  The result is
+ *   - a guaranteed enclosure  volume_lo <= vol{x in root : Query(x) < iso} <= volume_hi  (in the sense of QueryBounds: Query(x) is the
+ *     double this library computes; see "Why it holds" below),
+ *   - an estimate of the zeroth, first and second moments of that solid: volume, the integral of x (3 numbers) and of x x^T (6 numbers
+ *     in the order xx, yy, zz, xy, xz, yz),
+ *   - optionally the final cells themselves: an adaptive voxelisation of the solid and of a narrow band around its surface.
+ * The region is the whole root box.  Host, device and block entries run the same statements (csrc/integrate.hpp; every expression
+ * below has its association written, no multiply-add is fused, -ffp-contract=off) and give the same bits.
+ * Arguments: iso finite; depth D in 0..15; samples q in {1, 2, 4}; max_cells in 8..2^28.
+ *   A cell     is a leaf node n (tree depth d) at a relative level l >= 0 with integer coordinates in [0, 2^l)^3 inside the leaf; its
+ *              absolute depth is a = d + l.  In the leaf's unit coordinates, per axis with its coordinate m:
+ *                lo = -1.0 + (double)m * w,  w = 2.0 / (double)(1 << l);   hi = lo + w;   u_c = 0.5 * (lo + hi);   rho = 1.0 / (double)(1 << l)
+ *              -- all exact dyadics.  In the root's normalised frame p in [-0.5, 0.5]^3 its edge is s = 1.0 / (double)(1 << a) and, with
+ *              (i, j, k) its integer coordinates at depth a (the leaf's own coordinates shifted left by l, plus m), per axis
+ *                plo = -0.5 + (double)i * s;   c = plo + 0.5 * s                                         -- exact too.
+ *   Class      f_c = the leaf's polynomial at u_c, by the leaf evaluation Query uses
+ *              e   = HPSDF_SURFACE_SLACK * ((rho * G_0 + rho * G_1) + rho * G_2) + HPSDF_SURFACE_ETA * S
+ *              1 (outside) if f_c - iso > e;  else 2 (inside) if iso - f_c > e;  else 0 (undecided).
+ *              If f_c or e is not finite in any cell the whole call ends with status HPSDF_INTEGRATE_NOT_FINITE: unit_volume_lo = 0,
+ *              unit_volume_hi = 1 (volume_lo = 0, volume_hi = J), every estimate a quiet NaN, the counts 0, no cells.
+ *   Lists      List 0 holds the leaves in increasing node index, each at l = 0.  List l + 1 holds, for every cell of list l that is
+ *              undecided with a < D, in list order, its 8 children in child index order (x fastest: child ch has coordinates
+ *              2 i + (ch & 1), 2 j + ((ch >> 1) & 1), 2 k + (ch >> 2) at depth a + 1).  Positions in the next list come from an
+ *              exclusive scan of the split flags; no atomic decides an order.  If the next list would hold more than max_cells cells,
+ *              no cell of this level is split: the level is final and the status is HPSDF_INTEGRATE_CELL_LIMIT -- the result degrades
+ *              (a wider enclosure), it does not fail.  `levels` is l of the last list.
+ *   Final      A final cell is a decided cell at any level, or an undecided cell that is not split.  With v = (s * s) * s and the box
+ *              moments of a box of edge s, volume v and centre c
+ *                M0 = v;   M1_k = v * c_k;   M2_kk = v * (c_k * c_k + (s * s) / 12.0);   M2_jk = v * (c_j * c_k)
+ *              an inside cell adds v to unit_volume_lo and its box moments to the estimate; an outside cell adds nothing; an undecided
+ *              cell adds v to unit_volume_hi - unit_volume_lo and, for the estimate, takes its q^3 sub-boxes of edge ss = s * (1.0 / q),
+ *              x fastest, then y, then z: sub-box m per axis has its centre at u = lo + (double)(2 m + 1) * ((0.5 * w) * (1.0 / q)) in
+ *              the leaf and at p = plo + (double)(2 m + 1) * (0.5 * ss) in the root's frame (exact); the polynomial is evaluated at u,
+ *              and a sub-box with value < iso adds its box moments (edge ss, volume (ss * ss) * ss, centre p) to the cell's row, in
+ *              sub-box order, row = row + moments.
+ *   Sums       Volumes are exact: with D <= 15 and q <= 4 every volume term is a multiple of 2^-51 (a leaf is never deeper than
+ *              HPSDF_TREE_MAX_DEPTH), and every partial sum is at most 1, so no addition of volumes rounds and their order cannot
+ *              matter; unit_volume_lo, unit_volume_hi and unit_volume are exact rationals and unit_volume_lo <= unit_volume <=
+ *              unit_volume_hi holds exactly.  The cell counts are integers below 2^53 and go the same way.  First and second moments
+ *              are not exact; their sum is DEFINED: the rows of a list's cells (a split cell's row is zero) are taken in list order in
+ *              blocks of 256, zero-padded; lane t holds row t; for stride = 128, 64, ..., 1: x[t] = x[t] + x[t + stride] for t <
+ *              stride; the block sums are reduced by the same rule until one row is left; the level totals are added in increasing
+ *              l, ((T0 + T1) + T2) ...  The kernel keeps a cell's row in registers and writes one row per workgroup.
+ *   World      x_k = rootCentre_k + p_k * size_k with size_k = 1.0 / rootInvSizes_k and J = (size_0 * size_1) * size_2:
+ *                volume_lo = J * unit_volume_lo;   volume_hi = J * unit_volume_hi;   volume = J * M0
+ *                m1_k  = J * (rootCentre_k * M0 + size_k * M1_k)
+ *                m2_jk = J * (((rootCentre_j * rootCentre_k) * M0 + (rootCentre_j * size_k) * M1_k)
+ *                             + ((rootCentre_k * size_j) * M1_j + (size_j * size_k) * M2_jk))
+ *              computed on the host from the normalised sums (these four roundings are outside the guarantee: the guaranteed pair
+ *              is unit_volume_lo, unit_volume_hi).
+ * Why it holds, and why the existing constants cover this use (nothing was retuned).  The variation bound |f(u) - f(u_c)| <= tau^3
+ * sum_a rho_a G_a and the evaluation error 2^-41 S are QueryBounds' (above), with u_c and rho exact here -- the cell is GIVEN in unit
+ * coordinates, not mapped from world corners, so the 2^-45 S centre term does not even arise.  What replaces it: a point x of the cell
+ * reaches the leaf with u computed by Query from x through two subtractions and two multiplications, which may fall a few ulps (of
+ * 2, the unit cube's size: under 2^-50) outside [lo, hi]; sup |df/du_a| <= tau^3 G_a and G_a <= 78 S, so f moves by under 78 * 1.0268 *
+ * S * 2^-50 < 2^-43.6 S per axis, charged to ETA: 2^-40 + 3 * 2^-43.6 < 2^-39.6 S against ETA = 2^-32 S.  The comparison's left side
+ * f_c - iso is one rounding, relative 2^-53 of the very quantity compared with e, which the 0.4 % that SLACK leaves over tau^3
+ * takes.  The same rounding of x can carry a point within 2^-52 (relative) of a leaf's face into the neighbouring leaf, where another
+ * polynomial answers; these points form shells of relative thickness 2^-52 around leaf faces, and the enclosure is of the solid in
+ * the root's frame p, up to that measure.
+ * Outputs: hpsdf_integral (below); optionally *out_cells, a malloc'd array of the final cells (hpsdf_extract_surface's convention: the
+ * caller frees it; an empty result is NULL with *out_n_cells = 0; pass out_cells = out_n_cells = NULL to get none), in list order,
+ * level by level, 12 bytes a cell: the cell is [-0.5 + i * 2^-depth, -0.5 + (i + 1) * 2^-depth) x ... in p.  Over all final cells the
+ * volumes 8^-depth sum to 1: they tile the root.
+ * iso not finite, depth > 15, samples not 1, 2 or 4, max_cells outside 8..2^28, a NULL tree or `out`, only one of out_cells and
+ * out_n_cells NULL: HPSDF_ERR_INVALID_ARGUMENT, and nothing is written.  On any failure nothing stays allocated and the context stays
+ * usable.  hpsdf_integrate_device runs on the context stream (one classify kernel, one rocPRIM scan, one contribute kernel and the
+ * row reduction per level) and synchronises before it returns; list 0 and the leaves' constants are made by the first call on a tree and
+ * kept with it until hpsdf_tree_destroy.  hpsdf_integrate_host computes on the calling thread from the tree's host copies (fetched
+ * once), hpsdf_integrate_block from a serialised block with no device at all; it accepts and refuses blocks as
+ * hpsdf_query_bounds_block does.
+ * Not done: regions other than the root (no clipping to a sub-box); surface area; a linear reconstruction in the finest cells (the
+ * estimate is a q^3-point sign count there: first order in s it is not); rigorous bounds on the first and second moments beyond what
+ * |p_k| <= 0.5 gives from the undecided volume U = unit_volume_hi - unit_volume_lo (the true M1_k lies within U / 2 of the inside
+ * cells' sum, M2_kk within U / 4, M2_jk within U / 4). */
+enum { HPSDF_INTEGRATE_OK = 0, HPSDF_INTEGRATE_CELL_LIMIT = 1, HPSDF_INTEGRATE_NOT_FINITE = 2 };
+typedef struct hpsdf_integral {
+    double unit_volume_lo, unit_volume_hi, unit_volume; /* root-normalised, exact */
+    double volume_lo, volume_hi, volume;                /* world frame */
+    double m1[3], m2[6];                                /* world frame: the integrals of x and of xx, yy, zz, xy, xz, yz */
+    double unit_m1[3], unit_m2[6];                      /* the same in p */
+    uint64_t cells_inside, cells_outside, cells_undecided; /* final cells by class */
+    uint64_t evaluations;                               /* polynomial evaluations: the cells of all lists + q^3 per undecided final cell */
+    uint32_t status;                                    /* HPSDF_INTEGRATE_* */
+    uint32_t levels;                                    /* relative level of the last list */
+} hpsdf_integral;
+typedef struct hpsdf_integrate_cell {
+    uint32_t node;    /* the leaf's node index */
+    uint8_t depth;    /* absolute depth a */
+    uint8_t cls;      /* 0 undecided, 1 outside, 2 inside */
+    uint16_t i, j, k; /* integer coordinates at depth a */
+} hpsdf_integrate_cell;
+HPSDF_API int hpsdf_integrate_device(hpsdf_ctx* ctx, const hpsdf_tree* t, double iso, uint32_t depth, uint32_t samples, uint32_t max_cells,
+                                     hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_integrate_host(hpsdf_ctx* ctx, const hpsdf_tree* t, double iso, uint32_t depth, uint32_t samples, uint32_t max_cells,
+                                   hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_integrate_block(const void* block, size_t size, double iso, uint32_t depth, uint32_t samples, uint32_t max_cells,
+                                    hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+
 /* ---- Create: Octree::Create under the canonical round schedule ---------------
  * (Octree.cpp:312-352, 194-309, 558-659, 804-856, 1007-1093; schedule: DESIGN.md)
  *

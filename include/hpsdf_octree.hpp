@@ -698,6 +698,31 @@ class Octree {
         check(hpsdf_query_bounds_grid_host(ctx_, t, lo, hi, n, subdiv_, maxLeaves_, outLo, outHi, outStatus, outLeaves));
     }
 
+    /// Volume bounds and moments of the solid {Query < iso_} over the root (no reference counterpart; include/hpsdf.h, "Integrate"):
+    /// volume_lo <= volume <= volume_hi guaranteed, volume / m1 / m2 estimated, by refining the leaves into dyadic cells down to absolute
+    /// depth depth_ (0..15) where the leaves' bound cannot decide the sign; samples_ (1, 2 or 4) per axis in the cells left undecided;
+    /// maxCells_ (8..2^28) bounds every list of cells (status HPSDF_INTEGRATE_CELL_LIMIT: a wider enclosure, not a failure).  cells_
+    /// (optional) receives the final cells, in list order, level by level
+    hpsdf_integral Integrate(f64 iso_ = 0.0, uint32_t depth_ = 8, uint32_t samples_ = 2, uint32_t maxCells_ = 1u << 24,
+                             std::vector<hpsdf_integrate_cell>* cells_ = nullptr) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        hpsdf_integral r;
+        hpsdf_integrate_cell* cells = nullptr;
+        uint64_t n = 0;
+        check(hpsdf_integrate_device(ctx_, t, iso_, depth_, samples_, maxCells_, &r, cells_ ? &cells : nullptr, cells_ ? &n : nullptr));
+        if (cells_) {
+            try {
+                cells_->assign(cells, cells + n);
+            } catch (...) {
+                std::free(cells);
+                throw;
+            }
+            std::free(cells);
+        }
+        return r;
+    }
+
     /// Returns the aabb of the root node   (Octree.h:81)
     Eigen::AlignedBox3f GetRootAABB() const { return config_.root; }
 
