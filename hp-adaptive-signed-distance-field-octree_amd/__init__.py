@@ -138,6 +138,7 @@ _SIGNATURES = {
     "hpsdf_field_create_tree_csg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "hpsdf_field_destroy": (C.c_int, [C.c_void_p]),
     "hpsdf_field_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "hpsdf_field_mesh_arrays": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "hpsdf_field_eval_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hpsdf_field_eval_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hpsdf_field_eval_naive_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -484,6 +485,12 @@ class Context:
             pass
 
 
+# one 64-byte BVH node / slab record (csrc/device_types.hpp: BvhNode, NodeSlab), as Field.mesh_arrays returns them
+BVH_DTYPE = np.dtype([("lo0", np.float32, 3), ("hi0", np.float32, 3), ("lo1", np.float32, 3), ("hi1", np.float32, 3),
+                      ("c0", np.int32), ("c1", np.int32), ("pad", np.uint32, 2)])
+SLAB_DTYPE = np.dtype([("g0", np.float32, 4), ("n0", np.float32, 4), ("g1", np.float32, 4), ("n1", np.float32, 4)])
+
+
 class Field:
     def __init__(self, handle, keep=(), kind=None):
         self.handle = handle
@@ -579,6 +586,25 @@ class Field:
         check(lib().hpsdf_field_mesh_stats(self.handle, out, 1 if reset else 0))
         return dict(zip(("wave_queries", "node_visits", "tri_tests", "tri_test_lanes", "leaf_pairs", "bound_batches", "closest_batches",
                          "seed_exact"), (int(v) for v in out)))
+
+    def mesh_arrays(self, ctx=None):
+        """Mesh fields, diagnostics: host copies of what the field keeps on its device (read-only), as a dict of numpy arrays --
+        verts (nVerts, 3) f32, tris (nTris, 3) u32, triPos and triPre (nTris, 12) f32, halfEdges (3 nTris) u32, bvh (BVH_DTYPE) and slabs
+        (SLAB_DTYPE, or None for a field without them) -- with nVerts, nTris, nBvhNodes, leafLog2.  The field knows its device: ctx is
+        accepted for symmetry with the eval calls."""
+        info = (C.c_uint64 * 5)()
+        check(lib().hpsdf_field_mesh_arrays(self.handle, info, None, None))
+        nv, nt, nn, leaf_log2, has_slabs = (int(v) for v in info)
+        arrs = [np.empty((nv, 3), np.float32), np.empty((nt, 3), np.uint32), np.empty((nt, 12), np.float32), np.empty((nt, 12), np.float32),
+                np.empty(3 * nt, np.uint32), np.empty(nn, BVH_DTYPE), np.empty(nn if has_slabs else 0, SLAB_DTYPE)]
+        bufs = (C.c_void_p * 7)(*[a.ctypes.data if a.size else None for a in arrs])
+        caps = (C.c_uint64 * 7)(*[a.nbytes for a in arrs])
+        check(lib().hpsdf_field_mesh_arrays(self.handle, info, bufs, caps))
+        out = dict(zip(("verts", "tris", "triPos", "triPre", "halfEdges", "bvh", "slabs"), arrs))
+        if not has_slabs:
+            out["slabs"] = None
+        out.update(nVerts=nv, nTris=nt, nBvhNodes=nn, leafLog2=leaf_log2)
+        return out
 
     def release_host_copies(self):
         """Drops the host-side copies of a mesh field's arrays that calls of one or two points are answered from (they come back with

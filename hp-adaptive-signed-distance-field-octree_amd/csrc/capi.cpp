@@ -596,11 +596,39 @@ static size_t meshMirrorBytes(const hpsdf_field* f) {
     return (size_t)f->nVerts * 12 + (size_t)f->nTris * (12 + 12 + 4 * (size_t)(kTriRecordFloats + kTriPreFloats)) + (size_t)f->nBvhNodes * sizeof(BvhNode);
 }
 static size_t hostMeshMirrorLimit() { static const size_t v = hostLimit("HPSDF_HOST_MESH_MIRROR_MB", 512) << 20; return v; }
+// Where the host copies of a mesh field's device arrays go: the ONE list of what a mesh field holds on the device, for the mirror below
+// and for hpsdf_field_mesh_arrays.  A null destination is skipped; slabs exist on device-built fields only.  Reads the device, writes the host.
+struct MeshArraysDst {
+    float* verts = nullptr;
+    uint32_t* tris = nullptr;
+    float* triPos = nullptr;
+    float* triPre = nullptr;
+    uint32_t* halfEdges = nullptr;
+    BvhNode* bvh = nullptr;
+    NodeSlab* slabs = nullptr;
+};
+constexpr int kMeshArrays = 7;
+static void meshArrayBytes(const hpsdf_field* f, size_t bytes[kMeshArrays]) {
+    bytes[0] = 3 * (size_t)f->nVerts * sizeof(float), bytes[1] = 3 * (size_t)f->nTris * sizeof(uint32_t);
+    bytes[2] = (size_t)kTriRecordFloats * f->nTris * sizeof(float), bytes[3] = (size_t)kTriPreFloats * f->nTris * sizeof(float);
+    bytes[4] = 3 * (size_t)f->nTris * sizeof(uint32_t), bytes[5] = (size_t)f->nBvhNodes * sizeof(BvhNode);
+    bytes[6] = f->dSlabs ? (size_t)f->nBvhNodes * sizeof(NodeSlab) : 0;
+}
+static int meshDownload(const hpsdf_field* f, const MeshArraysDst& d) {
+    size_t bytes[kMeshArrays];
+    meshArrayBytes(f, bytes);
+    void* const dst[kMeshArrays] = {d.verts, d.tris, d.triPos, d.triPre, d.halfEdges, d.bvh, d.slabs};
+    const void* const src[kMeshArrays] = {f->dVerts, f->dTris, f->dTriPos, f->dTriPre, f->dHalfEdges, f->dBvh, f->dSlabs};
+    HPSDF_HIP(hipSetDevice(f->device));
+    HPSDF_HIP(hipDeviceSynchronize());  // (the field's arrays may still be being written on some stream)
+    for (int i = 0; i < kMeshArrays; ++i)
+        if (dst[i] && src[i] && bytes[i]) HPSDF_HIP(hipMemcpy(dst[i], src[i], bytes[i], hipMemcpyDeviceToHost));
+    return HPSDF_OK;
+}
 // The host copies of a mesh field's arrays (made once, by the first call of a few points)
 static int meshHostMirror(const hpsdf_field* f, std::shared_ptr<hpsdf_field::HostMirror>* out) {
     std::lock_guard<std::mutex> guard(f->hostMirrorLock);
     if (!f->hostMirror) {
-        HPSDF_HIP(hipSetDevice(f->device));
         auto m = std::make_shared<hpsdf_field::HostMirror>();
         m->verts.resize(3 * (size_t)f->nVerts);
         m->tris.resize(3 * (size_t)f->nTris);
@@ -608,23 +636,42 @@ static int meshHostMirror(const hpsdf_field* f, std::shared_ptr<hpsdf_field::Hos
         m->triPos.resize((size_t)kTriRecordFloats * f->nTris);
         m->triPre.resize((size_t)kTriPreFloats * f->nTris);
         m->bvh.resize(std::max<size_t>(1, f->nBvhNodes));
-        HPSDF_HIP(hipDeviceSynchronize());  // (the field's arrays may still be being written on some stream)
-        HPSDF_HIP(hipMemcpy(m->verts.data(), f->dVerts, m->verts.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HPSDF_HIP(hipMemcpy(m->tris.data(), f->dTris, m->tris.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HPSDF_HIP(hipMemcpy(m->halfEdges.data(), f->dHalfEdges, m->halfEdges.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HPSDF_HIP(hipMemcpy(m->triPos.data(), f->dTriPos, m->triPos.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HPSDF_HIP(hipMemcpy(m->triPre.data(), f->dTriPre, m->triPre.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if (f->nBvhNodes) HPSDF_HIP(hipMemcpy(m->bvh.data(), f->dBvh, (size_t)f->nBvhNodes * sizeof(BvhNode), hipMemcpyDeviceToHost));
+        MeshArraysDst dst;
+        dst.verts = m->verts.data(), dst.tris = m->tris.data(), dst.triPos = m->triPos.data(), dst.triPre = m->triPre.data();
+        dst.halfEdges = m->halfEdges.data(), dst.bvh = m->bvh.data();  // (no slabs: the per-point traversal uses boxes and triangle records only)
+        const int rc = meshDownload(f, dst);
+        if (rc) return rc;
         MeshDev& d = m->dev;
         d.verts = m->verts.data(), d.tris = m->tris.data(), d.halfEdges = m->halfEdges.data();
         d.triPos = reinterpret_cast<const float4*>(m->triPos.data());
         d.triPre = reinterpret_cast<const float4*>(m->triPre.data());
-        d.bvh = m->bvh.data(), d.slabs = nullptr;  // (the per-point traversal uses boxes and triangle records only)
+        d.bvh = m->bvh.data(), d.slabs = nullptr;
         d.nTris = f->nTris, d.nNodes = f->nBvhNodes, d.leafLog2 = f->leafLog2, d.poolCap = 0, d.stats = nullptr;
         f->hostMirror = m;
     }
     *out = f->hostMirror;
     return HPSDF_OK;
+}
+
+int hpsdf_field_mesh_arrays(const hpsdf_field* f, uint64_t info[5], void* const* buffers, const uint64_t* capacities) {
+    HPSDF_TRY
+    if (!f || !info || f->kind != kHostMesh || f->device < 0) return fail(HPSDF_ERR_INVALID_ARGUMENT, "not a mesh field");
+    if (buffers && !capacities) return fail(HPSDF_ERR_INVALID_ARGUMENT, "buffers without their capacities");
+    size_t bytes[kMeshArrays];
+    meshArrayBytes(f, bytes);
+    if (buffers) {
+        for (int i = 0; i < kMeshArrays; ++i)
+            if (buffers[i] && capacities[i] < bytes[i])
+                return fail(HPSDF_ERR_INVALID_ARGUMENT, "mesh array " + std::to_string(i) + " needs " + std::to_string(bytes[i]) + " bytes");
+        MeshArraysDst dst;
+        dst.verts = (float*)buffers[0], dst.tris = (uint32_t*)buffers[1], dst.triPos = (float*)buffers[2], dst.triPre = (float*)buffers[3];
+        dst.halfEdges = (uint32_t*)buffers[4], dst.bvh = (BvhNode*)buffers[5], dst.slabs = (NodeSlab*)buffers[6];
+        const int rc = meshDownload(f, dst);
+        if (rc) return rc;
+    }
+    info[0] = f->nVerts, info[1] = f->nTris, info[2] = f->nBvhNodes, info[3] = f->leafLog2, info[4] = f->dSlabs ? 1 : 0;
+    return HPSDF_OK;
+    HPSDF_CATCH
 }
 
 int hpsdf_field_release_host_copies(hpsdf_field* f) {

@@ -283,6 +283,13 @@ HPSDF_API int hpsdf_selftest_acosf(hpsdf_ctx* ctx, uint32_t first_bits, uint32_t
  * [4] (point, leaf) pairs queued, [5] wave-wide batches of lower-bound tests, [6] of closest-point tests, [7] points whose
  * seed (the leaf their own descent ended in) already held the answer.  Synchronises the device; reset != 0 zeroes the counters. */
 HPSDF_API int hpsdf_field_mesh_stats(const hpsdf_field* f, uint64_t out[8], int reset);
+/* Diagnostics (no reference counterpart; read-only): what a mesh field keeps on the device, copied to the host after a device-wide
+ * synchronisation -- the data every traversal prunes by (csrc/device_types.hpp has the layouts).  info[0..4] = vertices, triangles, BVH
+ * nodes, log2 of the largest leaf, 1 if the field has slabs.  buffers (null: only info is filled) and capacities (bytes) have seven
+ * entries: verts (3 f32 per vertex), tris (3 u32 per triangle), triPos and triPre (12 f32 per triangle / per leaf slot), halfEdges
+ * (3 u32 per triangle), bvh and slabs (64 bytes per BVH node); a null entry is skipped, the slabs' entry also when the field has none.
+ * HPSDF_ERR_INVALID_ARGUMENT for a field that is not a mesh and for a buffer smaller than its array: nothing is written then. */
+HPSDF_API int hpsdf_field_mesh_arrays(const hpsdf_field* f, uint64_t info[5], void* const* buffers, const uint64_t* capacities);
 
 /* ---- Query: Octree::FromMemoryBlock + Octree::Query (Octree.cpp:403-421, 662-702, 859-901) */
 /* block layout: [u64 nCoeffs][f64 x nCoeffs][u64 nNodes][hpsdf_node x nNodes][hpsdf_config] */
