@@ -127,8 +127,8 @@ uint64_t jobCost(int degree, int depth, bool coarse) {
     return c ? c : 1;
 }
 
-int builderBegin(hpsdf_build* b, const hpsdf_config* cfg, const hpsdf_build_opts* opts) {
-    // Config::IsValid, Source/HP/Config.cpp:17-32 (asserts there, status codes here)
+// Config::IsValid, Source/HP/Config.cpp:17-32 (asserts there, status codes here)
+int validateBuildConfig(const hpsdf_config* cfg) {
     if (!(cfg->target_error_threshold > 0.0)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "targetErrorThreshold must be > 0");
     if (cfg->thread_count == 0) return fail(HPSDF_ERR_INVALID_ARGUMENT, "threadCount must be > 0");
     {
@@ -140,11 +140,21 @@ int builderBegin(hpsdf_build* b, const hpsdf_config* cfg, const hpsdf_build_opts
     if (cfg->weighting_type != 0) {
         if (!(cfg->weighting_strength > 0.0)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "nearnessWeighting.strength must be > 0");
     }
+    return HPSDF_OK;
+}
+
+hpsdf_config configWithZeroedPads(const hpsdf_config* cfg) {
+    hpsdf_config c = *cfg;
+    std::memset(c.pad0, 0, sizeof c.pad0);
+    std::memset(c.pad1, 0, sizeof c.pad1);
+    std::memset(c.pad2, 0, sizeof c.pad2);
+    return c;
+}
+
+int builderBegin(hpsdf_build* b, const hpsdf_config* cfg, const hpsdf_build_opts* opts) {
+    if (const int rc = validateBuildConfig(cfg)) return rc;
     b->weighted = cfg->weighting_type != 0;
-    b->cfg = *cfg;
-    std::memset(b->cfg.pad0, 0, sizeof b->cfg.pad0);
-    std::memset(b->cfg.pad1, 0, sizeof b->cfg.pad1);
-    std::memset(b->cfg.pad2, 0, sizeof b->cfg.pad2);
+    b->cfg = configWithZeroedPads(cfg);
     if (opts) {
         if (opts->world < 1 || opts->rank < 0 || opts->rank >= opts->world)
             return fail(HPSDF_ERR_INVALID_ARGUMENT, "bad rank/world");

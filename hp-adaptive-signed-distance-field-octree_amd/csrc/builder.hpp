@@ -98,6 +98,9 @@ namespace hpsdf {
 
 uint64_t jobCost(int degree, int depth, bool coarse);
 
+// what both schedulers ask of a configuration before they build, and the copy of it that goes into the block
+int validateBuildConfig(const hpsdf_config* cfg);
+hpsdf_config configWithZeroedPads(const hpsdf_config* cfg);
 int builderBegin(hpsdf_build* b, const hpsdf_config* cfg, const hpsdf_build_opts* opts);
 int builderSelect(hpsdf_build* b, uint64_t* nJobs);
 int builderJobs(const hpsdf_build* b, hpsdf_job* out);

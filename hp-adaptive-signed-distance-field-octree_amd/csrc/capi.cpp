@@ -1610,26 +1610,30 @@ void hpsdf_ctx_set_block_allocator(hpsdf_ctx* ctx, hpsdf_block_alloc_fn alloc, h
     ctx->blockAlloc = alloc, ctx->blockRelease = alloc ? release : nullptr, ctx->blockUser = alloc ? user : nullptr;
 }
 
+// The tail of every Create (Octree.cpp:341-344): the continuity pass over a block that was built, when the configuration asks for it.
+// Several ranks run it each on their identical copy (deterministic: no exchange).  `rc` is the build's status and comes back
+// unless the pass itself fails: then the block is freed and the outputs are zeroed.
+static int continuityAfterCreate(hpsdf_ctx* ctx, const hpsdf_config* cfg, void** block, size_t* size, int rc) {
+    std::memset(&g_lastContinuity, 0, sizeof g_lastContinuity);
+    if (rc || !cfg->continuity_enforce) return rc;
+    std::string err;
+    rc = continuityPostProcess(*block, *size, 0.0, 0, 0, &g_lastContinuity, err, ctx);
+    if (rc) {
+        setError(err);
+        ctx->freeBlock(*block);
+        *block = nullptr;
+        *size = 0;
+    }
+    return rc;
+}
+
 int hpsdf_create(hpsdf_ctx* ctx, const hpsdf_config* cfg, const hpsdf_field* field, uint64_t K, void** block,
                  size_t* size, hpsdf_build_stats* stats) {
     HPSDF_TRY
     if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "Create runs on the GPU: a device context is required");
     if (!cfg || !field || !block || !size) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
-    if (frontierEligible(ctx, cfg, field, K)) {  // frontier, decision and bookkeeping on the device (frontier.hip)
-        int frc = frontierCreate(ctx, cfg, field, K, block, size, stats);
-        std::memset(&g_lastContinuity, 0, sizeof g_lastContinuity);
-        if (!frc && cfg->continuity_enforce) {  // Octree.cpp:341-344
-            std::string err;
-            frc = continuityPostProcess(*block, *size, 0.0, 0, 0, &g_lastContinuity, err, ctx);
-            if (frc) {
-                setError(err);
-                ctx->freeBlock(*block);
-                *block = nullptr;
-                *size = 0;
-            }
-        }
-        return frc;
-    }
+    if (frontierEligible(ctx, cfg, field, K))  // frontier, decision and bookkeeping on the device (frontier.hip)
+        return continuityAfterCreate(ctx, cfg, block, size, frontierCreate(ctx, cfg, field, K, block, size, stats));
     hpsdf_build_opts o;
     std::memset(&o, 0, sizeof o);
     o.max_jobs_per_round = K;
@@ -1680,17 +1684,7 @@ int hpsdf_create(hpsdf_ctx* ctx, const hpsdf_config* cfg, const hpsdf_field* fie
     }
     if (!rc && stats) hpsdf_build_get_stats(b, stats);
     t1 = now();
-    std::memset(&g_lastContinuity, 0, sizeof g_lastContinuity);
-    if (!rc && cfg->continuity_enforce) {  // Octree.cpp:341-344
-        std::string err;
-        rc = continuityPostProcess(*block, *size, 0.0, 0, 0, &g_lastContinuity, err, ctx);
-        if (rc) {
-            setError(err);
-            ctx->freeBlock(*block);
-            *block = nullptr;
-            *size = 0;
-        }
-    }
+    rc = continuityAfterCreate(ctx, cfg, block, size, rc);
     const double tCont = now() - t1;
     t1 = now();
     owner.reset();
@@ -1841,21 +1835,10 @@ int hpsdf_create_distributed(hpsdf_ctx* ctx, const hpsdf_config* cfg, const hpsd
     // (the device-side frontier packs a segment's owner rank into three bits: more than 8 ranks take the host scheduler's rounds)
     // (... and a weighted incremental fit needs the node's previous rows, which another rank may hold: the host scheduler's
     // sharded rounds hand them over)
-    int rc = (frontierEligible(ctx, cfg, field, K) && world <= 8)
-                 ? frontierCreate(ctx, cfg, field, K, block, size, stats, rank, world, gather, user)
-                 : createShardedOnHostScheduler(ctx, cfg, field, K, rank, world, gather, user, block, size, stats);
-    std::memset(&g_lastContinuity, 0, sizeof g_lastContinuity);
-    if (!rc && cfg->continuity_enforce) {  // Octree.cpp:341-344: every rank on its identical copy (deterministic: no exchange)
-        std::string err;
-        rc = continuityPostProcess(*block, *size, 0.0, 0, 0, &g_lastContinuity, err, ctx);
-        if (rc) {
-            setError(err);
-            ctx->freeBlock(*block);
-            *block = nullptr;
-            *size = 0;
-        }
-    }
-    return rc;
+    const int rc = (frontierEligible(ctx, cfg, field, K) && world <= 8)
+                       ? frontierCreate(ctx, cfg, field, K, block, size, stats, rank, world, gather, user)
+                       : createShardedOnHostScheduler(ctx, cfg, field, K, rank, world, gather, user, block, size, stats);
+    return continuityAfterCreate(ctx, cfg, block, size, rc);
     HPSDF_CATCH
 }
 

@@ -677,6 +677,40 @@ def test_device_frontier_equals_host_scheduler(H, ctx, monkeypatch, name, target
         assert sgot[k] == swant[k], k
 
 
+def test_both_schedulers_reject_a_bad_config_alike(H, ctx, monkeypatch):
+    """Config::IsValid (Config.cpp:17-32) is one function that both schedulers call before they launch anything: the device
+    frontier and the host scheduler answer a configuration they cannot build with the same status and the same message, and
+    the context builds again afterwards (the frontier's workspace was handed back)."""
+    from helpers import product_field
+
+    def weighted(wtype, strength):
+        c = H.make_config(1e-5)
+        c.nearnessWeighting_type, c.nearnessWeighting_strength = wtype, strength
+        return c
+
+    bad = [(H.make_config(0.0), "targetErrorThreshold must be > 0"),
+           (H.make_config(float("nan")), "targetErrorThreshold must be > 0"),
+           (H.make_config(1e-5, threads=0), "threadCount must be > 0"),
+           (H.make_config(1e-5, (-0.5, -0.5, -0.5), (0.5, 0.5, -0.5)), "root volume must be > 0"),
+           (weighted(1, 0.0), "nearnessWeighting.strength must be > 0"),
+           (weighted(2, float("nan")), "nearnessWeighting.strength must be > 0")]
+    f = product_field(H, "union3")
+    good = None
+    for cfg, msg in bad:
+        answers = []
+        for host in ("1", "0"):
+            monkeypatch.setenv("HPSDF_HOST_FRONTIER", host)
+            with pytest.raises(H.HpsdfError) as e:
+                H.create_block(ctx, cfg, f, 1024)
+            answers.append((e.value.status, str(e.value)))
+            blk, st = H.create_block(ctx, H.make_config(1e-5), f, 1024)  # the same context still builds
+            assert st["device_frontier"] == (host == "0")
+            good = good or blk
+            assert blk == good
+        assert answers[0] == answers[1], (msg, answers)
+        assert answers[0][0] == H.ERR_INVALID_ARGUMENT and msg in answers[0][1], answers
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("host", ["0", "1"])
 def test_block_allocator_receives_every_block(H, monkeypatch, host):
