@@ -247,6 +247,11 @@ float ora_mesh_signed_distance(const ora_mesh* m, const float p[3], uint64_t* tr
     return sign * sqrtf(v3_sqnorm(d));
 }
 
+/* The same scan at n points (xyz interleaved, float32): one call for a replay's millions of samples.  tri and simplex may be NULL. */
+void ora_mesh_signed_distance_batch(const ora_mesh* m, const float* pts, size_t n, float* out, uint64_t* tri, int* simplex) {
+    for (size_t i = 0; i < n; ++i) out[i] = ora_mesh_signed_distance(m, pts + 3 * i, tri ? tri + i : NULL, simplex ? simplex + i : NULL);
+}
+
 void ora_acosf_batch(uint32_t first, uint32_t stride, size_t n, float* out) {
     for (size_t i = 0; i < n; ++i) {
         const uint32_t b = first + (uint32_t)i * stride;

@@ -136,6 +136,8 @@ def lib():
     L.ora_acosf_batch.argtypes = [C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p]
     L.ora_mesh_signed_distance.restype = C.c_float
     L.ora_mesh_signed_distance.argtypes = [C.c_void_p, fp, u64p, C.POINTER(C.c_int)]
+    L.ora_mesh_signed_distance_batch.restype = None
+    L.ora_mesh_signed_distance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ora_set_reduction_order.argtypes = [C.c_int]
     L.ora_get_reduction_order.restype = C.c_int
     _LIB = L
@@ -252,6 +254,17 @@ class MeshField:
         self.f.mesh = self.handle
 
     def signed_distance(self, pts):
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        L = lib()
+        out = np.empty(len(pts), np.float32)
+        tri = np.empty(len(pts), np.uint64)
+        simp = np.empty(len(pts), np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        L.ora_mesh_signed_distance_batch(self.handle, vp(pts), len(pts), vp(out), vp(tri), vp(simp))
+        return out, tri, simp
+
+    def signed_distance_per_point(self, pts):
+        """The per-point entry, one call a point (what signed_distance was before the batched entry)."""
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
         L = lib()
         out = np.empty(len(pts), np.float32)

@@ -27,6 +27,26 @@ terms are products of two relative errors each below (n + 200) u < 2e-11, so eve
                                                                  => eF <= 4 (|p0 x| + |p1 y| + |p2 z| + |p3|)
    CSG     min / max / negation are exact and |min(a + alpha, b + beta) - min(a, b)| <= max(|alpha|, |beta|): eF = max of the operands'.
    The reduction order (hpsdf_set_reduction_order) only permutes the additions counted above; the bounds hold for both orders.
+   Data (DataField: a mesh, csrc/field_glue.hpp fieldEvalWorld, hp_oracle.c ora_field_eval ORA_FIELD_MESH; a sample buffer).  The
+           field IS a table of float64 numbers, one per sample position: there is no real-valued F behind it that the float64
+           value approximates.  For a mesh the number at position X (float64, reproduced bit for bit, section 2) is
+               (double) SignedDistanceAtPt((float) X_x, (float) X_y, (float) X_z).
+           The cast rounds to nearest and is reproduced bit for bit (numpy's astype(float32) is the same IEEE conversion); the
+           scan is float32 arithmetic that the oracle restates statement by statement and the kernels are pinned to bit for bit
+           (tests/test_gpu_parity.py, and the anchor of tests/test_gpu_hiprec_fields.py on the very positions used here), so its
+           float32 result is reproduced bit for bit; widening float32 to float64 is exact.  The three steps contribute
+           nothing:                                              => eF = 0
+           What such a fit checks is everything around the table -- the positions handed to it, their cast, which sample meets
+           which weight -- and the fit's own arithmetic; not whether the scan is the true distance (DESIGN.md section 2 says why
+           exact geometry is no reference for it).
+   Tree CSG (CsgField; applyCsg, Octree.cpp:355-400; ora_field_eval ORA_FIELD_TREE_CSG).  With o = FApprox(old tree, X) and
+           v = the inner field at X:  union min(o, v), intersect max(o, v), subtract max(-o, v) -- the reference negates the OLD
+           tree, as o * -1.0.  Negation and o * -1.0 are exact (a sign flip), min and max are exact, so the argument is the one for
+           analytic CSG above: |min(o + alpha, v + beta) - min(o, v)| <= max(|alpha|, |beta|), likewise for max.  The old tree's
+           value is section 3's: the descent and the unit coordinates are float64 operations reproduced bit for bit (a point ON a
+           face of an old leaf -- the centre node of every odd rule lies on one when the old leaves are deeper than the cell --
+           goes to the upper child, >= at :681-683, and Block.descend does the same), the series in long double with its bound
+           f_bound.  So alpha <= f_bound and               => eF = max(f_bound / u, eF of the inner field).
 
 2. A fit row r = (a, b, c) of degree p at depth d (Octree.cpp:1028-1056):
        c_r = sum_s t_s,   t_s = L_a(x_i) N_a L_b(x_j) N_b L_c(x_k) N_c * S w_i w_j w_k F(X_s),   n = (4p + 1)^3 samples,
@@ -128,8 +148,66 @@ def _sum3(a, b, c, left):
     return (a + b) + c if left else a + (b + c)
 
 
+class DataField:
+    """A field that is data (section 1): values(points_f64[n, 3]) -> float64[n], the numbers the fit is handed at the reproduced
+    sample positions, taken as exact (eF = 0)."""
+
+    def __init__(self, values):
+        self.values = values
+
+
+def mesh_field(mesh, mutant=None):
+    """A mesh as data.  mesh: an object with signed_distance(points_f32[n, 3]) -> (float32[n], ...) -- the oracle's O(n) scan
+    (O.MeshField), never a traversal or a fit of the product.  The positions are cast to float32 (round to nearest, as (float) x
+    does), the scan's float32 value is widened.  mutant "ulp": the positions one float32 ulp up before the cast."""
+    assert mutant in (None, "ulp"), mutant
+
+    def values(pts):
+        pts = np.asarray(pts, np.float64)
+        if mutant == "ulp":
+            pts = pts + np.spacing(pts.astype(np.float32)).astype(np.float64)
+        return mesh.signed_distance(np.ascontiguousarray(pts.astype(np.float32)))[0].astype(np.float64)
+    return DataField(values)
+
+
+class CsgField:
+    """(old_block, op, inner): the tree-CSG wrapper of Octree.cpp:355-400 around an inner field (a spec list or a DataField).
+    mutant (tests/test_hiprec_fields_cpu.py): "subtract_swapped" max(old, -F), "union_max", "tree_f32" the old tree evaluated at
+    the float32-cast point, "tie_low" a point on an old leaf's face sent to the lower child."""
+
+    def __init__(self, old_block, op, inner, mutant=None):
+        self.block = old_block if isinstance(old_block, Block) else Block(old_block)
+        self.op, self.inner, self.mutant = op, inner, mutant
+
+
+def _points(X, Y, Z):
+    shape = np.broadcast(X, Y, Z).shape
+    return np.stack([np.broadcast_to(np.asarray(v, np.float64), shape).ravel() for v in (X, Y, Z)], 1), shape
+
+
 def field_eval(spec, X, Y, Z, left=False):
-    """An analytic field (spec: [(kind, op, params)], as Field.analytic) at float64 points -> (value in long double, eF / u)."""
+    """A field at float64 points -> (value in long double, eF / u).  spec: an analytic field [(kind, op, params)] (as
+    Field.analytic), a DataField or a CsgField."""
+    if isinstance(spec, DataField):
+        pts, shape = _points(X, Y, Z)
+        v = np.asarray(spec.values(pts), np.float64)
+        return v.astype(LD).reshape(shape), np.zeros(shape)
+    if isinstance(spec, CsgField):
+        pts, shape = _points(X, Y, Z)
+        v, e = field_eval(spec.inner, X, Y, Z, left)
+        v, e = np.broadcast_to(v, shape), np.broadcast_to(e, shape)
+        tp = pts.astype(np.float32).astype(np.float64) if spec.mutant == "tree_f32" else pts
+        old = fapprox_batch(spec.block, tp, tie_low=spec.mutant == "tie_low")
+        o = old["f"].reshape(shape)
+        if spec.op == OP_UNION:
+            out = np.maximum(o, v) if spec.mutant == "union_max" else np.minimum(o, v)
+        elif spec.op == OP_SUBTRACT:
+            out = np.maximum(o, -v) if spec.mutant == "subtract_swapped" else np.maximum(-o, v)
+        elif spec.op == OP_INTERSECT:
+            out = np.maximum(o, v)
+        else:
+            raise ValueError(spec.op)
+        return out, np.maximum(e, (old["f_bound"] / U).reshape(shape))
     x, y, z = (np.asarray(v, np.float64).astype(LD) for v in (X, Y, Z))
     acc = acc_e = None
     for kind, op, p in spec:
@@ -182,10 +260,27 @@ def _contract(mx, my, mz, t):
     return np.einsum("ck,Cabk->Cabc", mz, g2)
 
 
+def sample_axes(root_min, root_max, bmin, bmax, nq):
+    """The world coordinates of a fit's samples, per axis, as the reference and the kernels form them in float64 -> ([3] arrays
+    [C, nq], the cells' float64 half-extents [C, 3]).  Sample (i, j, k) of cell C lies at (wx[0][C, i], wx[1][C, j], wx[2][C, k])."""
+    bmin = np.atleast_2d(np.asarray(bmin, np.float32))
+    bmax = np.atleast_2d(np.asarray(bmax, np.float32))
+    x, _ = rule(nq)
+    # :1020-1022, the product's FitTask: sizes() and center() in float32, then widened
+    scale = (bmax - bmin).astype(np.float64) * 0.5
+    centre = ((bmin + bmax) / np.float32(2.0)).astype(np.float64)
+    rmin, rmax = np.asarray(root_min, np.float32), np.asarray(root_max, np.float32)
+    rb = (rmax - rmin).astype(np.float64)
+    rc = ((rmin + rmax) / np.float32(2.0)).astype(np.float64)
+    # :1039 and :327 (fit_kernels.hpp: w = u * bounds + centre): float64, unfused
+    return [(x[None, :] * scale[:, a:a + 1] + centre[:, a:a + 1]) * rb[a] + rc[a] for a in range(3)], scale
+
+
 def fit_reference(spec, root_min, root_max, bmin, bmax, degree, depth, left=False, *, order=None, nl_depth=None,
                   samples_f32=False, zero_sample=None):
     """Octree::FitPolynomial of `degree` at `depth` for cells bmin, bmax ([C, 3] float32, root-normalised) under the root
-    [root_min, root_max] -> dict(c=[C, ncoef] long double, bound=[C, ncoef], e=[C] long double, e_bound=[C]).
+    [root_min, root_max] -> dict(c=[C, ncoef] long double, bound=[C, ncoef], e=[C] long double, e_bound=[C]).  spec: whatever
+    field_eval takes -- an analytic spec, a DataField or a CsgField.
     The keyword arguments build mutants (tests/test_hiprec_cpu.py): another Gauss order, NormalisedLengths of another depth,
     samples rounded to float32, one sample's weight zeroed (its (i, j, k))."""
     bmin = np.atleast_2d(np.asarray(bmin, np.float32))
@@ -194,14 +289,7 @@ def fit_reference(spec, root_min, root_max, bmin, bmax, degree, depth, left=Fals
     p = degree
     nq = 4 * p + 1 if order is None else order
     x, w = rule(nq)
-    # :1020-1022, the product's FitTask: sizes() and center() in float32, then widened
-    scale = (bmax - bmin).astype(np.float64) * 0.5
-    centre = ((bmin + bmax) / np.float32(2.0)).astype(np.float64)
-    rmin, rmax = np.asarray(root_min, np.float32), np.asarray(root_max, np.float32)
-    rb = (rmax - rmin).astype(np.float64)
-    rc = ((rmin + rmax) / np.float32(2.0)).astype(np.float64)
-    # :1039 and :327 (fit_kernels.hpp: w = u * bounds + centre): float64, unfused
-    wx = [(x[None, :] * scale[:, a:a + 1] + centre[:, a:a + 1]) * rb[a] + rc[a] for a in range(3)]
+    wx, scale = sample_axes(root_min, root_max, bmin, bmax, nq)
     X = np.broadcast_to(wx[0][:, :, None, None], (C, nq, nq, nq))
     Y = np.broadcast_to(wx[1][:, None, :, None], (C, nq, nq, nq))
     Zc = np.broadcast_to(wx[2][:, None, None, :], (C, nq, nq, nq))
@@ -283,8 +371,9 @@ class Block:
         inv = (np.float32(1.0) / (self.root_max - self.root_min)).astype(np.float64)
         return np.asarray(q, np.float64) / inv + rc
 
-    def descend(self, q):
-        """Octree.cpp:668-702 on root-normalised points (all inside the root) -> leaf index per point."""
+    def descend(self, q, tie_low=False):
+        """Octree.cpp:668-702 on root-normalised points (all inside the root) -> leaf index per point.  tie_low: the mutant that
+        sends a point on a face to the lower child (> for >=)."""
         cur = np.zeros(len(q), np.int64)
         out = np.full(len(q), -1, np.int64)
         live = np.arange(len(q))
@@ -293,7 +382,8 @@ class Block:
             half = (self.bmax[n, 0] - self.bmin[n, 0]) * np.float32(0.5)       # :679 the x extent on every axis
             idx = np.zeros(len(live), np.int64)
             for a in range(3):
-                idx += (q[live, a] >= (self.bmin[n, a] + half).astype(np.float64)).astype(np.int64) << a
+                mid = (self.bmin[n, a] + half).astype(np.float64)
+                idx += (q[live, a] > mid if tie_low else q[live, a] >= mid).astype(np.int64) << a
             ch = self.child[n].astype(np.int64) + idx
             leaf = self.degree[ch] != INTERIOR
             out[live[leaf]] = ch[leaf]
@@ -359,6 +449,41 @@ def fapprox_reference(block, points, gradient=False, rec=REC):
     if gradient:
         out["g"], out["g_bound"] = g, gb
     return out
+
+
+def fapprox_batch(block, points, tie_low=False):
+    """fapprox_reference's value and bound (no gradient) for many points, leaves of one (degree, depth) at a time: the same
+    long-double operations in the same order, vectorised over the points -> dict(f, f_bound, leaf)."""
+    blk = block if isinstance(block, Block) else Block(block)
+    q = blk.to_unit(points)
+    leaf = blk.descend(q, tie_low)
+    f, fb = np.empty(len(q), LD), np.empty(len(q))
+    key = blk.degree[leaf] * 16 + blk.depth[leaf]
+    for k in np.unique(key):
+        deg, dep = int(k) // 16, int(k) % 16
+        nc = int(COUNT[deg])
+        a, b, c = BIDX[:nc, 0], BIDX[:nc, 1], BIDX[:nc, 2]
+        Nd = NL[:deg + 1, dep].astype(LD)
+        Nf = (Nd[a] * Nd[b] * Nd[c]).astype(np.float64)
+        sel = np.nonzero(key == k)[0]
+        step = max(1, 2 ** 19 // nc)
+        for i in range(0, len(sel), step):
+            s = sel[i:i + step]
+            n = leaf[s]
+            cen = ((blk.bmin[n] + blk.bmax[n]) / np.float32(2.0)).astype(np.float64)
+            x = (q[s] - cen) * float(2 << dep)                   # :862, float64
+            co = blk.coeffs[blk.start[n][:, None] + np.arange(nc)[None, :]]
+            L = [legendre_ld(x[:, j], deg) for j in range(3)]     # [deg + 1, m] each
+            Lf = [L[j] * Nd[:, None] for j in range(3)]
+            t = co.astype(LD) * Lf[0][a].T * Lf[1][b].T * Lf[2][c].T
+            cs = np.cumsum(t, axis=1)
+            run = np.abs(cs[:, 1:]).astype(np.float64).sum(1)
+            Lab = [np.abs(L[j]).astype(np.float64) for j in range(3)]
+            la, lb, lc = Lab[0][a].T, Lab[1][b].T, Lab[2][c].T
+            rec_t = a ** 2 * lb * lc + b ** 2 * la * lc + c ** 2 * la * lb
+            f[s] = cs[:, -1]
+            fb[s] = U * ((np.abs(co) * Nf * (rec_t + K_Q * la * lb * lc)).sum(1) + run) * SLACK
+    return {"f": f, "f_bound": fb, "leaf": leaf}
 
 
 def points_in_leaves(block, rng, n, margin=2.0 ** -20):

@@ -73,6 +73,11 @@ No number below was chosen by looking at a kernel's or the oracle's output.
    decisions, the selection, the totals, B and the stop's consistency.  Section 5 applies as it stands: weighting changes no row,
    and a weighted build's rows have the provenance of an unweighted one's -- which is what shows a stale copied row.
    WEIGHT_MUTANTS are defects of this section alone (tests/test_hiprec_weight_cpu.py shows each one rejected).
+
+7. Fields.  The replay sees the field only through hiprec.fit_reference: `spec` is an analytic field, a mesh as data (hiprec.DataField,
+   eF = 0) or either under the tree-CSG wrapper (hiprec.CsgField, eF from the old tree's Query bound) -- hiprec.py section 1 -- and
+   every error keeps the bound that fit gives it.  Sections 1 to 5 do not change (tests/test_hiprec_fields_cpu.py,
+   tests/test_gpu_hiprec_fields.py).
 """
 import numpy as np
 
@@ -161,7 +166,9 @@ def coarse_tree():
 
 # ---------------------------------------------------------------------------------------------------------------- fits, cached
 class Fits:
-    """fit_reference per (cell, degree, depth[, NormalisedLengths' depth]), batched by shape and computed once."""
+    """fit_reference per (cell, degree, depth[, NormalisedLengths' depth]), batched by shape and computed once.  spec: whatever
+    hiprec.field_eval takes -- an analytic spec, a DataField (a mesh as data) or a CsgField; replay_free, Guided and
+    check_leaf_rows hand theirs through to here and look at nothing else of it."""
 
     def __init__(self, spec, root, left=False):
         self.spec, self.root, self.left = spec, (tuple(root[0]), tuple(root[1])), left
@@ -335,6 +342,7 @@ class _State:
         self.dropped = {}
         self.hist = {}                                                    # leaf -> [p0, [degrees appended since]]
         self.counts = {"rounds": 0, "jobs": 0, "p_refines": 0, "h_refines": 0, "dropped": 0}
+        self.job_log = {}                                                 # (stored degree, depth, coarse) -> jobs applied
 
     def job_tuple(self, n, coarse):
         return (self.t.bmin[n], self.t.bmax[n], self.t.degree[n], self.t.depth[n], coarse, COARSE_DEGREE if coarse else self.hist[n][0])
@@ -343,6 +351,8 @@ class _State:
         """One result (:253-290) on the tree and the queue; the caller moves the totals."""
         t = self.t
         self.counts["jobs"] += 1
+        k = (int(t.degree[n]), int(t.depth[n]), bool(coarse))
+        self.job_log[k] = self.job_log.get(k, 0) + 1
         old = self.queue.pop(n)
         if action == "P":
             if coarse:
@@ -374,13 +384,13 @@ class _State:
     def result(self):
         out = self.t.arrays()
         out.update(history={n: (p0, tuple(app)) for n, (p0, app) in self.hist.items()}, counts=dict(self.counts), fits=self.fits,
-                   weighting=self.weighting)
+                   weighting=self.weighting, job_log=dict(self.job_log))
         return out
 
 
 def replay_free(spec, root, target, K, rounds, left=False, mutant=None, fits=None, weighting=None):
     """Grow the tree from long-double errors alone for exactly `rounds` rounds (section 4: the stop itself is not decidable) ->
-    dict(child, degree, depth, bmin, bmax, history, counts, undecided_decisions, undecided_selections, min_margin,
+    dict(child, degree, depth, bmin, bmax, history, counts, job_log, undecided_decisions, undecided_selections, min_margin,
     stop_consistent, true_total, true_bound, B, fits, weighting).  weighting: None, (type, strength) or a W.Weighting (its cache
     of weights is then shared): every error below is the weighted one (section 6)."""
     s = _State(spec, root, left, fits, weighting, mutant)
@@ -514,7 +524,8 @@ class Guided:
         assert drift <= self.tot.B + tb, (drift, self.tot.B, tb)
         out = dict(self.worst)
         out.update(drift=drift, B=self.tot.B, drift_over_B=drift / self.tot.B, true_total=tt, true_bound=tb, f64_total=float(self.tot.f64),
-                   small_rounds=self.small_rounds, history=s.result()["history"], counts=dict(s.counts), weighting=s.weighting)
+                   small_rounds=self.small_rounds, history=s.result()["history"], counts=dict(s.counts), weighting=s.weighting,
+                   job_log=dict(s.job_log))
         return out
 
 
