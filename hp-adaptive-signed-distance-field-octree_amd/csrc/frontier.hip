@@ -39,199 +39,20 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <vector>
+#include <cstdint>
 
-#include "block.hpp"
-#include "builder.hpp"
-#include "frontier.hpp"
-#include "launch.hpp"
-#include "runtime.hpp"
+#include "frontier_dev.hpp"
 
 namespace hpsdf {
 
 namespace {
 
-constexpr uint32_t kFrJobs = 4096;  // largest batch: K <= 4096, and round 0 is the 4096 depth-4 cells
-constexpr uint32_t kFrTasks = 9 * kFrJobs;
-constexpr int kFrSegs = 10;         // degrees 2..11: the first fit and at most nine P-refinements
-constexpr int kFrDepths = kMaxDepth + 2;
-constexpr int kFrClasses = 2 * (kMaxDegree + 1) * kFrDepths;  // (degree, from scratch | incremental, depth)
-constexpr uint64_t kNotQueued = ~0ull;
-constexpr uint64_t kOffMask = (1ull << 56) - 1;  // a segment's arena offset; the bits above hold the rank that owns it
 constexpr uint32_t kFrSort = 4096;  // bitonic sort capacity (LDS): the fallback ordering of a batch
 constexpr uint32_t kFrExact = 64;   // candidates left when the digit-by-digit refinement hands over to exact ranking
-// Multi-rank builds: the last double of a rank's part of errs is its STATUS for the round's exchange.  A healthy rank zeroes it
-// (fr_init_kernel, the round kernel's leader or fr_batch_kernel); a rank whose share of the round failed on the host (device memory) sets it to all ones and
-// enters the exchange all the same; the round kernel's leader finds it (frPeerCheck) and every rank leaves with an error instead of
-// waiting in a later collective for a rank that has gone.
-constexpr uint32_t kFrStatusPad = 8;
-
-struct FrHdr {
-    uint32_t nNodes, nQueued, nJobs, done;
-    uint32_t round, maxDegree, maxDepth, overflow;
-    uint32_t nTasks, nBlocks, takenCount, candCount;
-    uint32_t above;   // selection, level 0: queued nodes in the exponent bins above the threshold bin t1
-    int32_t t1;       // (-1: the whole frontier is the batch); both are left by the previous round's update kernel
-    uint32_t nLeaves, arrive;
-    uint32_t degBlocks[13][2];  // {first block, count} per degree: the range a fit launch walks
-    uint32_t degTasks[13][2];   // {first task, count} per degree: the range a mesh-sampler launch walks
-    uint32_t lowTasks[13][2];   // {first task, count} per degree: the from-scratch fits that are split (FitBlock::split), i.e. the
-                                // range fit_mfma_low_kernel walks for the rows below the top degree
-    uint64_t arenaUsed, sampleUsed, nCoeffs, pad1;
-    uint64_t jobs, pRefines, hRefines, dropped, fits, samples;
-    uint64_t splitFits;   // from-scratch fits whose lower rows came from the split's second kernel (hpsdf_build_stats::split_fits)
-    uint32_t splitRound, padR;  // FrDev::splitFit if the round being prepared splits its from-scratch fits, else 0 (decided by the batch)
-    uint64_t roundBase, partStride;  // FrDev::replica: the round's fits write arena rows [roundBase + r partStride, + partStride) on rank r
-    double total, target;
-    // staging between the decide and update kernels of a round
-    uint32_t rP, rH, rD, rMaxDeg;
-    uint32_t rOps, rPad;
-    uint32_t sliceFirst[9];  // multi-rank: rank r computes jobs [sliceFirst[r], sliceFirst[r + 1]) of the round
-    uint32_t padS;
-    uint64_t packCount[8];   // multi-rank: coefficients rank r contributes to the packed store
-    uint64_t dbg[24];  // phase time stamps (s_memtime) of the one-workgroup kernels, read under HPSDF_TRACE
-    int64_t rCoeffDelta;
-    double rTotal;
-    uint32_t opsArrive, stuck;  // fr_round_kernel: update workgroups whose operands are written; a wait that ran out (never, by construction)
-    uint32_t chainStamp;  // round + 1 once rTotal holds that round's running total
-    uint32_t landed;      // (mirror only) the build's stamp, written when round 0's closing launch starts: the fit before it has finished, so
-                          // the rows it wrote into pinned host memory are there
-    uint32_t stored[2];   // (mirror only) the build's stamp once fr_store_kernel's node array / coefficients are in pinned host memory
-    uint32_t storeArrive[2];  // workgroups of fr_store_kernel that have finished a phase
-    uint32_t hist1[2048];  // queued nodes per exponent bin (kept by update / batch)
-    uint32_t hist2[2048];  // level-1 digits of the candidates of the current selection (grid selection only)
-    uint64_t agg[kFrJobs / 128];  // fr_round_kernel: per update workgroup {round stamp, splitting jobs << 16 | P jobs}
-};
-constexpr size_t kFrHdrCopyBytes = offsetof(FrHdr, hist1);
 static_assert(kFrHdrCopyBytes / 4 <= 1024, "frMirror copies the header with one thread a word");
-static inline void frCpuRelax() {  // the host's spin on the header mirror
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield");
-#endif
-}
-
-struct FrRound {  // shape classes of the current round (written by fr_batch_kernel, read by fr_tasks_kernel)
-    uint32_t cCount[kFrClasses], cFirst[kFrClasses], cCursor[kFrClasses], cBlockFirst[kFrClasses], cBlocks[kFrClasses];
-    uint64_t cArena[kFrClasses], cSample[kFrClasses];
-    uint64_t cArenaO[8][kFrClasses];  // FrDev::replica: arena rows before class c within owner o's part of the round
-    uint8_t cG[kFrClasses], cPlanes[kFrClasses];
-    uint64_t arenaBase;
-};
-
-struct FrDev {
-    FrHdr* hdr;
-    FrHdr* hostHdr;  // the header's mirror in pinned host memory, as the device addresses it
-    FrRound* rnd;
-    hpsdf_node* nodes;
-    uint64_t* qErr;     // bit pattern of the queued error; kNotQueued = not in the frontier
-    uint32_t* parent;
-    uint64_t* segOff;   // [node][kFrSegs] arena offsets (doubles)
-    uint8_t* segFirst;  // degree of the node's first segment
-    uint32_t* sub;      // coefficients below every interior node (kept incrementally from round 1 on)
-    uint32_t* taken;    // selection: nodes taken so far (unordered)
-    uint32_t* candA;
-    uint32_t* candB;
-    const uint32_t* batchIdx;  // the round's jobs in node-index order (round 0: the template's)
-    const double* batchErr;
-    const uint64_t* jobP;      // per job: arena offset of the P result / of the first H child
-    const uint64_t* jobH;
-    uint32_t* wBatchIdx;       // the same buffers, writable (rounds > 0)
-    double* wBatchErr;
-    uint64_t* wJobP;
-    uint64_t* wJobH;
-    double* ops;               // the round's additions to the running total, densely, in job order
-    uint32_t* jobRecA;         // per job of the round being opened, for fr_emit_kernel: H slot | P slot << 16 | degree << 28
-    uint16_t* jobRecB;         //   coarse | ours << 1 | owner << 2 | depth << 5
-    FitTask* tasks;
-    FitBlock* blocks;
-    double* errs;       // [jobs][9]
-    double* store;      // the finished block's coefficients and, behind them, its node array: pinned host memory as the device addresses it
-    const double* arena;
-    uint32_t nodeCap, K;
-    // multi-rank builds (world > 1): this rank fits a cost-balanced slice of every round's jobs
-    int32_t rank, world;
-    uint32_t errStride;    // doubles per rank in errs: rank r's slice sits at errs + r * errStride (all-gathered in place)
-    uint32_t errStrideNext;  // ... in the round being prepared (round 0 exchanges 4096 jobs' errors, later rounds K)
-    uint8_t* jobOwner;     // per job: the rank that fits it
-    uint32_t* packPos;     // [node][kFrSegs]: where the segment sits in its owner's pack buffer
-    double* pack;          // [world][packStride] all-gathered pack buffers (this rank writes its own)
-    uint64_t packStride;
-    int32_t fastFit;       // degrees >= 4 fitted by fit_mfma.hip: 16 cells per workgroup
-    int32_t splitFit;      // 0, or the lowest degree (.. 11) whose from-scratch fits are split: top-degree rows exact, the rest by fit_low_kernel.
-                           // Whether a round does split is the batch's decision (FrHdr::splitRound), by the host scheduler's rule
-    uint64_t sampleCap;    // doubles the sample buffer holds (the split's hand-over needs the round's samples to fit)
-    // nearness weighting (Octree.cpp:1071-1092, 1209-1247): a fit keeps ONE full coefficient array (an incremental fit
-    // carries the old rows over, :847), fit_weight_kernel leaves |mean FApprox| of every fit in `means`, the host turns
-    // the means into weights with its libm (pow / exp: what the oracle calls) and fr_weigh_kernel scales the errors
-    uint32_t buildStamp;  // a number of the build (FrHdr::landed)
-    uint32_t stamps;      // HPSDF_TRACE: the one-workgroup kernels leave their phases' times in FrHdr::dbg (a store a phase, and the next barrier waits for it)
-    double target;         // targetErrorThreshold of the build (the header is initialised before the build is known: FrontierWorkspace::clean)
-    int32_t weighted;
-    // Weighted builds on several ranks: every rank's arena is a REPLICA.  An incremental weighted fit carries the cell's previous rows
-    // over (:847), and those may have been fitted anywhere -- so a round's fits are laid out owner by owner at the same offsets on every
-    // rank (FrHdr::roundBase / partStride), every rank fills its own part, and ONE in-place all-gather of the round's part of the arena
-    // (beside the errors') leaves every rank with every row.  Segments then need no owner, the packed store no exchange of its own.
-    int32_t replica;
-    double* means;          // [jobs][9], pinned host memory as the device addresses it (written by fit_weight_kernel)
-    const double* weights;  // [jobs][9], pinned host memory as the device addresses it (written by the host)
-    uint32_t* hostFlag;     // pinned: {jobs of the round, stamp}: "the means are there"
-};
-
-__host__ __device__ inline uint32_t frCoef(int p) { return p == 6 ? 83u : (uint32_t)((p + 1) * (p + 2) * (p + 3) / 6); }
-__host__ __device__ inline int frClass(int degree, bool incr, int depth) { return (2 * degree + (incr ? 1 : 0)) * kFrDepths + depth; }
-__host__ __device__ inline size_t frLds(int degree, int g, int planes) {  // = fitLdsBytes (fit.hip)
-    const size_t nq = 4 * (size_t)degree + 1;
-    return ((size_t)(degree + 1) * nq + 2 * nq + 8 * (size_t)g + (size_t)g * planes * nq * nq) * sizeof(double);
-}
-// workgroup shape of `count` fits of one class: what fitShape (fit.hip) gives an unweighted, sampled-or-analytic fit
-// splitFit: 0 = off, else the lowest degree whose from-scratch fits are split (the context's splitMinDegree)
-constexpr size_t kFrFitLdsCap = 45 * 1024;
-__host__ __device__ inline bool frSplit(int splitFit, int degree, bool incr) { return splitFit > 0 && !incr && degree >= splitFit && degree <= 11; }
-__host__ __device__ inline void frShape(int degree, bool incr, uint32_t count, int* cells, int* planes, bool fast = false, bool weighted = false,
-                                        int split = 0) {
-    if (fast && degree >= 4 && degree <= 11) {  // the matrix-core fit: one workgroup = one tile of 16 cells
-        *cells = kMfmaCells, *planes = 1;
-        return;
-    }
-    if (frSplit(split, degree, incr)) incr = true;  // the exact kernel fits the top-degree rows only: the shape of an incremental fit
-    const int nrows = incr ? (int)(frCoef(degree) - frCoef(degree - 1)) : (int)frCoef(degree);
-    int gmax = nrows > kFitBlockThreads ? 1 : kFitBlockThreads / nrows;
-    // (45 KB of dynamic LDS + the fit kernel's 7 KB of static keep three workgroups on a CU at every degree.  Up to kFitMaxLdsBytes the
-    // incremental fits of degrees 6, 8, 9 and 11 stacked one or two cells more -- and a round launched for "one degree more than the
-    // host knows" ran two workgroups a CU: 238 us instead of 194)
-    while (gmax > 1 && frLds(degree, gmax, 1) > (weighted ? kFitMaxLdsBytes : kFrFitLdsCap)) --gmax;
-    uint32_t spread = (count + 511u) / 512u;
-    int cap = gmax;
-    if (degree == 2) {  // as fitShape: measured best for degree 2
-        if (count <= 4096u) spread = (count + 1023u) / 1024u;
-        cap = gmax < 16 ? gmax : 16;
-    }
-    int g = (int)(spread < 1u ? 1u : spread);
-    g = g < cap ? g : cap;
-    const int nq = 4 * degree + 1;
-    int pl = nq;
-    while (pl > 1 && frLds(degree, g, pl) > kFitChunkLdsBytes) --pl;
-    if (weighted) {  // as fitShape: the sample region is reused for the full coefficient array + 100 FApprox values of every cell
-        const int need = (int)frCoef(degree) + 100;
-        const int minPlanes = (need + nq * nq - 1) / (nq * nq);
-        const int want = nq < minPlanes ? nq : minPlanes;
-        pl = pl > want ? pl : want;
-        while (g > 1 && frLds(degree, g, pl) > kFitMaxLdsBytes) --g;
-    }
-    *cells = g;
-    *planes = pl;
-}
 
 // where job j's 9 errors sit: in the slice of the rank that fitted it
 __device__ __forceinline__ size_t frErrSlot(const FrDev& d, const FrHdr* h, uint32_t j) {
@@ -1113,9 +934,6 @@ __global__ __launch_bounds__(256) void fr_tasks_kernel(FrDev d) {
 // ---------------------------------------------------------------------------------------------------------------------
 // fr_round_kernel: closes a round (Octree.cpp:243-299 in node-index order, :594-601 per job, :216) and opens the next
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kFrInlineNodes = 131072;  // trees up to here are selected by the closing workgroup itself (128 passes of 1024 lanes; its bitmap
-                                             // holds 262 144 nodes.  65 536 sent union3 @ 4.5e-9, K = 4096 -- 58 k nodes + 32 k of room for a round -- to the
-                                             // grid selection in its last rounds: 5.8 ms against 4.5)
 constexpr unsigned long long kFrWaitTicks = 200000000ull;  // two seconds of the 100 MHz clock: a wait this long means a workgroup is gone
 
 // one lane waits until *p >= want, then acquires (the counter's writers release before they add); false: the wait ran out
@@ -1882,14 +1700,6 @@ __global__ __launch_bounds__(256) void fr_weigh_kernel(FrDev d, uint32_t stride,
 
 // per-build initialisation: the uniformly refined tree (a copy of the context's template) and the header.  Round 0's
 // batch, tasks and workgroups are the template's, used in place.
-struct FrTemplate {
-    const hpsdf_node* nodes;
-    const uint32_t* parent;
-    const uint32_t* sub;
-    uint32_t nNodes, nLeaves, nTasks, nBlocks;  // nTasks / nBlocks / arenaRows / samples: this rank's share of round 0
-    uint64_t arenaRows, samples;
-    uint32_t sliceFirst[9];
-};
 __global__ __launch_bounds__(256) void fr_init_kernel(FrDev d, FrTemplate t) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < t.nNodes) {
@@ -1932,1099 +1742,56 @@ __global__ __launch_bounds__(256) void fr_init_kernel(FrDev d, FrTemplate t) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host side
+// The launchers (frontier_dev.hpp), in the kernels' order.  The driver says how large the problem is; the grid and the
+// workgroup -- the kernel's __launch_bounds__ and what one workgroup of it takes on -- are decided here, beside the kernel.
 // ---------------------------------------------------------------------------------------------------------------------
-struct FrontierWorkspace {
-    int device = -1;
-    bool inUse = false;
-    FrDev d{};
-    FrHdr* hostHdr = nullptr;  // pinned
-    uint32_t nodeCap = 0;
-    uint64_t arenaCap = 0, sampleCap = 0;
-    double* arena = nullptr;
-    double* samples = nullptr;
-    // Template of the uniformly refined tree (Octree::UniformlyRefine, :112-191) and of round 0, which is the same for
-    // every build: the 4096 depth-4 cells in index order, one from-scratch degree-2 fit each, cell j's rows at arena
-    // offset 10 j (index order is the depth-first order of ReallocCoeffs, so a build that stops after round 0 finds
-    // its packed coefficient store already sitting at the start of the arena).
-    FrTemplate tmpl{};
-    hpsdf_node* tmplNodes = nullptr;
-    uint32_t* tmplParent = nullptr;
-    uint32_t* tmplSub = nullptr;
-    uint32_t* tmplLeaves = nullptr;
-    double* tmplErr = nullptr;
-    uint64_t* tmplJobP = nullptr;
-    FitTask* tmplTasks = nullptr;
-    FitBlock* tmplBlocks = nullptr;
-    size_t tmplLds = 0;
-    // fr_init_kernel has run for (cleanRank, cleanWorld) and nothing since: a build that ends well leaves the workspace ready for the
-    // next one (the launch runs while the host hands the block over), so a Create starts with its first fit
-    bool clean = false;
-    bool lastWentOn = false;  // this context's last build went on past round 0 (fr_round_kernel's flag bit 1: a guess about timing, never about results)
-    int cleanRank = -1, cleanWorld = -1;
-    uint32_t buildStamp = 0;
-    std::vector<hpsdf_node> hostNodesAfterRound0;  // the node array of a tree that stops after round 0, serialised
-    char* pinned = nullptr;                        // staging of the finished block
-    double* pinnedDev = nullptr;                   // ... as the device addresses it
-    size_t pinnedCap = 0;
-    // weighted builds: the round's |mean FApprox| values as the device writes them, the weights as the host answers, the
-    // "means are there" word pair (pinned, coherent: both sides watch them while the other writes)
-    double* hostMeans = nullptr;
-    double* hostWeights = nullptr;
-    uint32_t* hostFlag = nullptr;
-    uint32_t flagStamp = 0;
-    hipError_t ensureWeighting() {
-        if (hostMeans) return hipSuccess;
-        const size_t n = 8 * ((size_t)kFrJobs * HPSDF_JOB_HEADER_DOUBLES + kFrStatusPad);  // (indexed like errs: up to eight ranks' parts)
-        hipError_t e = hipHostMalloc((void**)&hostMeans, n * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&hostWeights, n * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&hostFlag, 64, hipHostMallocCoherent | hipHostMallocMapped);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&d.means, hostMeans, 0);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&d.weights, hostWeights, 0);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&d.hostFlag, hostFlag, 0);
-        if (e == hipSuccess) {
-            std::memset(hostMeans, 0, n * sizeof(double));
-            for (size_t i = 0; i < n; ++i) hostWeights[i] = 1.0;
-            hostFlag[0] = hostFlag[1] = 0;
-        }
-        return e;
-    }
-    // A round's fits are one launch per degree, and none of them fills the chip (a few hundred workgroups of two per CU):
-    // degrees beyond the first go to side streams and run beside it
-    static constexpr int kSide = 3;
-    hipStream_t side[kSide] = {nullptr, nullptr, nullptr};
-    hipEvent_t forkEv = nullptr, joinEv[kSide] = {nullptr, nullptr, nullptr};
-
-    template <typename T>
-    static hipError_t grow(T** p, size_t oldCount, size_t newCount, hipStream_t s, bool keep) {
-        T* np = nullptr;
-        hipError_t e = hipMalloc((void**)&np, newCount * sizeof(T));
-        if (e != hipSuccess) return e;
-        if (*p) {
-            if (keep && oldCount) e = hipMemcpyAsync(np, *p, oldCount * sizeof(T), hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            (void)hipFree(*p);
-        }
-        *p = np;
-        return e;
-    }
-    // device bytes per node of capacity (ensureNodes' arrays; hpsdf_ctx_set_build_limits counts with it)
-    static constexpr uint64_t kBytesPerNode = sizeof(hpsdf_node) + sizeof(uint64_t) /* qErr */ + 2 * sizeof(uint32_t) /* parent, segFirst */ +
-                                              (uint64_t)kFrSegs * sizeof(uint64_t) /* segOff */ + sizeof(uint64_t) /* sub */ + 2 * sizeof(uint32_t) /* candA, candB */;
-    hipError_t ensureNodes(uint32_t need, hipStream_t s) {
-        if (need <= nodeCap) return hipSuccess;
-        uint32_t nc = nodeCap ? nodeCap : 65536u;
-        while (nc < need) nc *= 2;
-        hipError_t e = grow(&d.nodes, nodeCap, nc, s, true);
-        if (e == hipSuccess) e = grow(&d.qErr, nodeCap, nc, s, true);
-        if (e == hipSuccess) e = grow(&d.parent, nodeCap, nc, s, true);
-        if (e == hipSuccess) e = grow(&d.segOff, (size_t)nodeCap * kFrSegs, (size_t)nc * kFrSegs, s, true);
-        if (e == hipSuccess) e = grow(&d.segFirst, nodeCap, nc, s, true);
-        if (e == hipSuccess) e = grow(&d.sub, nodeCap, nc, s, true);
-        if (e == hipSuccess) e = grow(&d.candA, nodeCap, nc, s, false);
-        if (e == hipSuccess) e = grow(&d.candB, nodeCap, nc, s, false);
-        if (e == hipSuccess && d.packPos) {
-            e = grow(&d.packPos, 0, (size_t)nc * kFrSegs, s, false);
-            if (e == hipSuccess) packPosCap = nc;
-        }
-        if (e == hipSuccess) nodeCap = nc, d.nodeCap = nc;
-        return e;
-    }
-    hipError_t ensureArena(uint64_t need, uint64_t used, hipStream_t s) {
-        if (need <= arenaCap) return hipSuccess;
-        uint64_t nc = arenaCap ? arenaCap : (1ull << 22);
-        while (nc < need) nc *= 2;
-        hipError_t e = grow(&arena, used, nc, s, true);
-        if (e == hipSuccess) arenaCap = nc, d.arena = arena;
-        return e;
-    }
-    hipError_t ensureSamples(uint64_t need, hipStream_t s) {
-        if (need <= sampleCap) return hipSuccess;
-        const uint64_t nc = (need + (1ull << 20) - 1) & ~((1ull << 20) - 1);  // to the need (GBs at high degrees), not to a power of two
-        hipError_t e = grow(&samples, 0, nc, s, false);
-        if (e == hipSuccess) sampleCap = nc;
-        return e;
-    }
-    // multi-rank: errs is [world][4096 * 9], plus owners, pack positions, round-0 share
-    int ranksCap = 1;
-    uint64_t packCap = 0;
-    FitTask* r0Tasks = nullptr;
-    FitBlock* r0Blocks = nullptr;
-    uint64_t* r0JobP = nullptr;
-    int r0Rank = -1, r0World = -1;  // what (rank, world, error stride, replica) the three r0 arrays were built for
-    bool r0Replica = false;
-    uint32_t r0ErrStride = 0;
-    std::vector<FitTask> hostTmplTasks, hostR0Tasks;
-    hipError_t ensureRanks(int world, hipStream_t s) {
-        hipError_t e = hipSuccess;
-        if (world > ranksCap) {
-            e = grow(&d.errs, 0, (size_t)world * (kFrJobs * HPSDF_JOB_HEADER_DOUBLES + kFrStatusPad), s, false);
-            if (e == hipSuccess) ranksCap = world;
-        }
-        if (e == hipSuccess && world > 1 && !d.jobOwner) {
-            e = hipMalloc((void**)&d.jobOwner, kFrJobs);
-            if (e == hipSuccess) e = hipMalloc((void**)&r0Tasks, kFrJobs * sizeof(FitTask));
-            if (e == hipSuccess) e = hipMalloc((void**)&r0Blocks, kFrJobs * sizeof(FitBlock));
-            if (e == hipSuccess) e = hipMalloc((void**)&r0JobP, kFrJobs * sizeof(uint64_t));
-        }
-        if (e == hipSuccess && world > 1 && packPosCap < nodeCap) {
-            e = grow(&d.packPos, 0, (size_t)nodeCap * kFrSegs, s, false);
-            if (e == hipSuccess) packPosCap = nodeCap;
-        }
-        return e;
-    }
-    uint32_t packPosCap = 0;
-    hipError_t ensurePack(uint64_t need, hipStream_t s) {
-        if (need <= packCap) return hipSuccess;
-        uint64_t nc = packCap ? packCap : (1ull << 20);
-        while (nc < need) nc *= 2;
-        hipError_t e = grow(&d.pack, 0, nc, s, false);
-        if (e == hipSuccess) packCap = nc;
-        return e;
-    }
-    hipError_t ensurePinned(size_t need) {
-        if (need <= pinnedCap) return hipSuccess;
-        size_t nc = pinnedCap ? pinnedCap : (1u << 20);
-        while (nc < need) nc *= 2;
-        if (pinned) (void)hipHostFree(pinned);
-        pinned = nullptr, pinnedDev = nullptr, pinnedCap = 0;
-        hipError_t e = hipHostMalloc((void**)&pinned, nc, hipHostMallocCoherent | hipHostMallocMapped);  // (round 0's fit writes it while the host may look)
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&pinnedDev, pinned, 0);
-        if (e == hipSuccess) pinnedCap = nc;
-        return e;
-    }
-    template <typename T>
-    static hipError_t upload(T** dst, const std::vector<T>& v) {
-        hipError_t e = hipMalloc((void**)dst, std::max<size_t>(1, v.size()) * sizeof(T));
-        if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-        return e;
-    }
-    hipError_t init(int dev, hipStream_t s) {
-        device = dev;
-        hipError_t e = hipMalloc((void**)&d.hdr, sizeof(FrHdr));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.rnd, sizeof(FrRound));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&hostHdr, sizeof(FrHdr), hipHostMallocCoherent | hipHostMallocMapped);  // (the host watches it while kernels write it)
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&d.hostHdr, hostHdr, 0);
-        if (e == hipSuccess) e = hipMalloc((void**)&d.taken, (kFrJobs + 64) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.wBatchIdx, kFrJobs * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.wBatchErr, kFrJobs * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.wJobP, kFrJobs * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.wJobH, kFrJobs * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.ops, (size_t)kFrJobs * 9 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.jobRecA, kFrJobs * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.jobRecB, kFrJobs * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.tasks, kFrTasks * sizeof(FitTask));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.blocks, kFrTasks * sizeof(FitBlock));
-        if (e == hipSuccess) e = hipMalloc((void**)&d.errs, (size_t)kFrJobs * HPSDF_JOB_HEADER_DOUBLES * sizeof(double));
-        if (e != hipSuccess) return e;
-        d.batchIdx = d.wBatchIdx, d.batchErr = d.wBatchErr, d.jobP = d.wJobP, d.jobH = d.wJobH;
-        // the uniformly refined tree, from the host scheduler's own initialisation (builderBegin): identical indices
-        hpsdf_build b;
-        hpsdf_config cfg;
-        hpsdf_config_default(&cfg);
-        cfg.thread_count = 1;
-        if (builderBegin(&b, &cfg, nullptr) != HPSDF_OK) return hipErrorUnknown;
-        const uint32_t nT = (uint32_t)b.nodes.size();
-        std::vector<uint32_t> parent(nT, 0), leaves, sub(nT, 0);
-        for (uint32_t i = 0; i < nT; ++i) {
-            if (b.nodes[i].child_idx != ~0ull)
-                for (unsigned c = 0; c < 8; ++c) parent[b.nodes[i].child_idx + c] = i;
-            else
-                leaves.push_back(i);
-        }
-        const uint32_t nL = (uint32_t)leaves.size();
-        if (nL > kFrJobs) return hipErrorUnknown;
-        for (uint32_t i = nT; i-- > 1;) {  // children have larger indices than their parents
-            const uint32_t own = b.nodes[i].child_idx == ~0ull ? frCoef(2) : sub[i];
-            sub[parent[i]] += own;
-        }
-        // round 0: class (degree 2, from scratch, depth 4), slot j = job j
-        int g = 1, pl = 1;
-        frShape(2, false, nL, &g, &pl);
-        std::vector<FitTask> tasks(nL);
-        std::vector<uint64_t> jobP(nL);
-        std::vector<double> errs(nL, HPSDF_INITIAL_NODE_ERR);
-        for (uint32_t j = 0; j < nL; ++j) {
-            const hpsdf_node& n = b.nodes[leaves[j]];
-            FitTask& t = tasks[j];
-            std::memset(&t, 0, sizeof t);
-            for (int a = 0; a < 3; ++a) t.bmin[a] = n.aabb_min[a], t.bmax[a] = n.aabb_max[a];
-            t.outOff = (uint64_t)j * frCoef(2);
-            t.copyOff = ~0ull;
-            t.sampleOff = (uint64_t)j * 729;
-            t.errSlot = j * HPSDF_JOB_HEADER_DOUBLES;
-            t.depth = n.depth;
-            t.pad[0] = 2;
-            jobP[j] = t.outOff;
-        }
-        std::vector<FitBlock> blocks((nL + g - 1) / g);
-        for (uint32_t k = 0; k < blocks.size(); ++k) {
-            FitBlock& fb = blocks[k];
-            std::memset(&fb, 0, sizeof fb);
-            fb.firstTask = k * (uint32_t)g;
-            fb.nTasks = (uint16_t)std::min<uint32_t>((uint32_t)g, nL - k * (uint32_t)g);
-            fb.degree = 2;
-            fb.planesPerChunk = (uint8_t)pl;
-            fb.rowStart = 0, fb.rowEnd = (uint16_t)frCoef(2);
-            fb.depth = b.nodes[leaves[0]].depth;
-        }
-        tmplLds = frLds(2, g, pl);
-        hostTmplTasks = tasks;
-        hostNodesAfterRound0 = b.nodes;
-        for (uint32_t j = 0; j < nL; ++j) {
-            hostNodesAfterRound0[leaves[j]].degree = 2;
-            hostNodesAfterRound0[leaves[j]].coeffs_start = (uint64_t)j * frCoef(2);
-        }
-        e = upload(&tmplNodes, b.nodes);
-        if (e == hipSuccess) e = upload(&tmplParent, parent);
-        if (e == hipSuccess) e = upload(&tmplSub, sub);
-        if (e == hipSuccess) e = upload(&tmplLeaves, leaves);
-        if (e == hipSuccess) e = upload(&tmplErr, errs);
-        if (e == hipSuccess) e = upload(&tmplJobP, jobP);
-        if (e == hipSuccess) e = upload(&tmplTasks, tasks);
-        if (e == hipSuccess) e = upload(&tmplBlocks, blocks);
-        tmpl.nodes = tmplNodes, tmpl.parent = tmplParent, tmpl.sub = tmplSub;
-        tmpl.nNodes = nT, tmpl.nLeaves = nL, tmpl.nTasks = nL, tmpl.nBlocks = (uint32_t)blocks.size();
-        tmpl.arenaRows = (uint64_t)nL * frCoef(2), tmpl.samples = (uint64_t)nL * 729;
-        for (int k = 0; k < kSide && e == hipSuccess; ++k) {
-            e = hipStreamCreateWithFlags(&side[k], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&joinEv[k], hipEventDisableTiming);
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&forkEv, hipEventDisableTiming);
-        if (e == hipSuccess) e = ensureNodes(65536, s);
-        if (e == hipSuccess) e = ensureArena(1ull << 22, 0, s);
-        if (e == hipSuccess) e = ensurePinned(4u << 20);
-        return e;
-    }
-    ~FrontierWorkspace() {
-        if (device >= 0) (void)hipSetDevice(device);
-        for (void* p : {(void*)d.hdr, (void*)d.rnd, (void*)d.nodes, (void*)d.qErr, (void*)d.parent, (void*)d.segOff, (void*)d.segFirst,
-                        (void*)d.sub, (void*)d.taken, (void*)d.candA, (void*)d.candB, (void*)d.wBatchIdx, (void*)d.wBatchErr, (void*)d.wJobP,
-                        (void*)d.wJobH, (void*)d.ops, (void*)d.jobRecA, (void*)d.jobRecB, (void*)d.tasks, (void*)d.blocks, (void*)d.errs,
-                        (void*)arena, (void*)samples, (void*)tmplNodes, (void*)tmplParent, (void*)tmplSub, (void*)tmplLeaves, (void*)tmplErr,
-                        (void*)tmplJobP, (void*)tmplTasks, (void*)tmplBlocks, (void*)d.jobOwner, (void*)d.packPos, (void*)d.pack, (void*)r0Tasks,
-                        (void*)r0Blocks, (void*)r0JobP})
-            if (p) (void)hipFree(p);
-        if (hostHdr) (void)hipHostFree(hostHdr);
-        if (pinned) (void)hipHostFree(pinned);
-        if (hostMeans) (void)hipHostFree(hostMeans);
-        if (hostWeights) (void)hipHostFree(hostWeights);
-        if (hostFlag) (void)hipHostFree(hostFlag);
-        for (int k = 0; k < kSide; ++k) {
-            if (side[k]) (void)hipStreamDestroy(side[k]);
-            if (joinEv[k]) (void)hipEventDestroy(joinEv[k]);
-        }
-        if (forkEv) (void)hipEventDestroy(forkEv);
-    }
-};
-
-bool frontierEligible(const hpsdf_ctx* ctx, const hpsdf_config* cfg, const hpsdf_field* field, uint64_t K) {
-    if (const char* e = std::getenv("HPSDF_HOST_FRONTIER"))
-        if (e[0] == '1') return false;
-    if (cfg->weighting_type > 2) return false;    // (unknown weighting: the host scheduler reports it)
-    if (cfg->enable_logging) return false;        // the per-job log line is printed by the host scheduler
-    const hpsdf_field* in = innermost(field);
-    if (!in || (in->kind != kHostAnalytic && in->kind != kHostMesh)) return false;  // callbacks are sampled by host threads
-    if (in->kind == kHostMesh) {
-        const char* e = std::getenv("HPSDF_MESH_FUSED");
-        if (e && e[0] == '1') return false;
-        if (meshFaceRuleReference(ctx)) return false;  // (the sampler's shared traversal assumes the default face rule: builder.cpp fits with the per-point one)
-    }
-    const uint64_t k = K ? K : HPSDF_DEFAULT_JOBS_PER_ROUND;
-    return k <= kFrJobs;
+hipError_t frLaunchSelect(hipStream_t stream, const FrDev& d, uint32_t nodes) {  // a node a lane, grid-stride beyond 512 workgroups
+    hipLaunchKernelGGL(fr_select_kernel, dim3(std::min<uint32_t>(512u, (nodes + 255u) / 256u)), dim3(256), 0, stream, d);
+    return hipGetLastError();
 }
-
-// A launch that failed (LDS over-subscription, a grid beyond the limits) used to surface a round later as "a round ended without
-// advancing": every launch of the build loop reports its own failure at once.
-#define FR_LAUNCH(kernel, grid, block, stream, ...)                                         \
-    do {                                                                                    \
-        hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                    \
-        const hipError_t le_ = hipGetLastError();                                           \
-        if (le_ != hipSuccess) return ::hpsdf::hipFail(le_, "launch of " #kernel);          \
-        if (frSyncEveryLaunch()) {                                                          \
-            std::fprintf(stderr, "[frontier] " #kernel " ...");                             \
-            const hipError_t se_ = hipStreamSynchronize(stream);                            \
-            std::fprintf(stderr, " %s\n", hipGetErrorString(se_));                          \
-        }                                                                                   \
-    } while (0)
-static bool frSyncEveryLaunch() {  // HPSDF_FRONTIER_SYNC=1: a fault names its kernel (diagnostic; the host's waits then find every round closed)
-    static const bool on = std::getenv("HPSDF_FRONTIER_SYNC") != nullptr;
-    return on;
+hipError_t frLaunchEmit(hipStream_t stream, const FrDev& d, uint32_t jobs) {  // 128 jobs a workgroup, eight lanes a job
+    hipLaunchKernelGGL(fr_emit_kernel, dim3((jobs + 127u) / 128u), dim3(1024), 0, stream, d);
+    return hipGetLastError();
 }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Create's driver: what the steps of a build share (file-level rules, the failure protocol, FrontierBuild), then the steps
-// ---------------------------------------------------------------------------------------------------------------------
-namespace {
-
-inline double frNow() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// The device tells the host that something is there by writing a word of pinned memory behind a system-scope fence.  Watching that
-// word costs ~3 us; waking up from hipStreamSynchronize ~20.  Watches for `microseconds` and says whether the word arrived: what a
-// caller falls back on when it did not (the ordinary wait, as a rule) and its acquire fence are the caller's.
-inline bool watchWord(const volatile uint32_t* word, uint32_t want, double microseconds) {
-    const double limit = frNow() + microseconds;
-    while (*word != want && frNow() < limit) frCpuRelax();
-    return *word == want;
+hipError_t frLaunchBatch(hipStream_t stream, const FrDev& d) {  // one workgroup
+    hipLaunchKernelGGL(fr_batch_kernel, dim3(1), dim3(1024), 0, stream, d);
+    return hipGetLastError();
 }
-
-// launch-time LDS of a fit launch of `deg`: the largest shape the device may pick
-std::vector<size_t> makeLdsTable(bool w) {
-    std::vector<size_t> t(kMaxDegree + 1, 0);
-    for (int deg = 1; deg <= kMaxDegree; ++deg)
-        for (int incr = 0; incr < 2; ++incr) {
-            int g, pl;
-            frShape(deg, incr != 0, 1u << 20, &g, &pl, false, w);  // g = the class's largest
-            for (int gg = 1; gg <= g; ++gg) {
-                const int nq = 4 * deg + 1;
-                int pp = nq;
-                while (pp > 1 && frLds(deg, gg, pp) > kFitChunkLdsBytes) --pp;
-                if (w) {  // frShape's weighted adjustment
-                    const int minPlanes = ((int)frCoef(deg) + 100 + nq * nq - 1) / (nq * nq);
-                    pp = std::max(pp, std::min(nq, minPlanes));
-                    if (gg > 1 && frLds(deg, gg, pp) > kFitMaxLdsBytes) continue;  // (frShape stacks fewer cells)
-                }
-                t[deg] = std::max(t[deg], frLds(deg, gg, pp));
-            }
-        }
-    return t;
+hipError_t frLaunchTasks(hipStream_t stream, const FrDev& d, uint32_t jobs) {  // sixteen lanes a job
+    hipLaunchKernelGGL(fr_tasks_kernel, dim3((16u * jobs + 255u) / 256u), dim3(256), 0, stream, d);
+    return hipGetLastError();
 }
-const std::vector<size_t>& fitLdsTable(bool weighted) {
-    static const std::vector<size_t> fitLdsPlain = makeLdsTable(false), fitLdsWeighted = makeLdsTable(true);
-    return weighted ? fitLdsWeighted : fitLdsPlain;
+hipError_t frLaunchRound(hipStream_t stream, const FrDev& d, uint32_t jobs, int flags) {  // workgroup 0 and the running total's, 128 jobs each in between
+    hipLaunchKernelGGL(fr_round_kernel, dim3(2 + (jobs + 127u) / 128u), dim3(1024), 0, stream, d, flags);
+    return hipGetLastError();
 }
-uint64_t rowsPerJob(int pmax) {  // arena rows one job can need when no leaf exceeds degree pmax
-    const int p = std::min(pmax, kMaxDegree - 1);
-    return (uint64_t)8 * frCoef(p) + frCoef(std::min(p + 1, kMaxDegree));
+hipError_t frLaunchSubtree(hipStream_t stream, const FrDev& d, uint32_t nodes) {  // a node a lane
+    hipLaunchKernelGGL(fr_subtree_kernel, dim3((nodes + 255u) / 256u), dim3(256), 0, stream, d);
+    return hipGetLastError();
 }
-uint64_t samplesPerJob(int pmax) {
-    const uint64_t a = 4 * (uint64_t)std::min(pmax, kMaxDegree - 1) + 1, b = a + 4;
-    return 8 * a * a * a + b * b * b;
+hipError_t frLaunchStore(hipStream_t stream, const FrDev& d, uint32_t nodes) {  // kStoreNodes a workgroup
+    hipLaunchKernelGGL(fr_store_kernel, dim3((nodes + kStoreNodes - 1u) / kStoreNodes), dim3(256), 0, stream, d);
+    return hipGetLastError();
 }
-
-// Round 0 on several ranks: rank r fits cells [ends[r], ends[r + 1]) of the template's nLeaves.  Equal costs, so the slices end
-// where the scheduler's rule puts them (builderSelect: the first i with i c >= total (r + 1) / world); ends beyond `world` are nLeaves.
-// Depends on the template and the world size alone, so it is known before anything can fail.
-void round0SliceEnds(uint32_t nLeaves, int world, uint32_t ends[9]) {
-    ends[0] = 0;
-    for (int r = 1; r < 9; ++r) ends[r] = nLeaves;
-    const uint64_t c = (uint64_t)frCoef(2) * 729ull, total = c * nLeaves;
-    uint32_t start = 0;
-    for (int r = 0; r < world; ++r) {
-        uint32_t end = nLeaves;
-        if (r + 1 < world) {
-            const uint64_t target = total * (uint64_t)(r + 1) / (uint64_t)world;
-            end = (uint32_t)((target + c - 1) / c);
-            end = std::min(std::max(end, start), nLeaves);
-        }
-        ends[r + 1] = end;
-        start = end;
-    }
+hipError_t frLaunchPackPos(hipStream_t stream, const FrDev& d) {  // one workgroup
+    hipLaunchKernelGGL(fr_packpos_kernel, dim3(1), dim3(1024), 0, stream, d);
+    return hipGetLastError();
 }
-// replica: doubles per rank in round 0's part of the arena (rank r's cells at r x this -- equal parts for the in-place all-gather)
-uint64_t round0PartRows(const uint32_t ends[9], int world) {
-    uint32_t maxCount = 1;
-    for (int r = 0; r < world; ++r) maxCount = std::max(maxCount, ends[r + 1] - ends[r]);
-    return ((uint64_t)maxCount * frCoef(2) + 15ull) & ~15ull;
+hipError_t frLaunchPack(hipStream_t stream, const FrDev& d, uint32_t nodes) {  // a node a wave, grid-stride beyond 2048 workgroups
+    hipLaunchKernelGGL(fr_pack_kernel, dim3(std::min<uint32_t>(2048u, (nodes + 3u) / 4u)), dim3(256), 0, stream, d);
+    return hipGetLastError();
 }
-
-void fillStats(const FrHdr* hh, uint64_t nNodes, uint64_t nCoeffs, int fitMode, hpsdf_build_stats* stats) {
-    std::memset(stats, 0, sizeof *stats);
-    stats->rounds = hh->round, stats->jobs = hh->jobs, stats->p_refines = hh->pRefines, stats->h_refines = hh->hRefines;
-    stats->dropped = hh->dropped, stats->fits = hh->fits, stats->samples = hh->samples;
-    stats->n_nodes = nNodes, stats->n_leaves = hh->nLeaves, stats->n_coeffs = nCoeffs, stats->total_error = hh->total;
-    stats->fit_mode = (uint64_t)fitMode, stats->split_fits = hh->splitFits, stats->device_frontier = 1;
+hipError_t frLaunchMeansDone(hipStream_t stream, const FrDev& d, uint32_t stamp) {  // one lane works
+    hipLaunchKernelGGL(fr_means_done_kernel, dim3(1), dim3(64), 0, stream, d, stamp);
+    return hipGetLastError();
 }
-
-// Several ranks: which exchanges the other ranks enter next.  If this rank's share fails while one is pending, it still enters it
-// -- with its status slot set (kFrStatusPad) -- before it returns its error: the others then leave with HPSDF_ERR_STATE instead of
-// waiting for a rank that has gone (FrontierBuild::leaveAfterFailure).
-struct PendingExchange {
-    enum Errors { kNone, kRound0, kLaterRound } errors = kNone;
-    uint32_t errStride = 0;  // of that exchange: where this rank leaves its status
-    // replica: the round's part of the arena while its exchange is still to come -- a failing rank enters it too, so round 0's part is
-    // known before anything can fail.  Kept as an OFFSET into the arena (doubles) and a size: the arena can move between the moment
-    // the part is known and the moment a failure sends this rank into the exchange (ensureArena reallocates), and a pointer taken
-    // earlier would then name freed memory.
-    bool rows = false;
-    uint64_t rowsOff = 0;
-    size_t rowsBytes = 0;
-
-    void round0Begins(uint32_t stride0) { errors = kRound0, errStride = stride0; }
-    void rowsAt(uint64_t off, size_t bytes) { rows = true, rowsOff = off, rowsBytes = bytes; }  // (round 0, the header, the batch kernel)
-    void rowsEntered() { rows = false; }  // (a gather that fails is the callback's failure, not a reason to enter it again)
-    void afterRound0Exchanges(uint32_t strideK) { errors = kNone, errStride = strideK; }
-    void afterHeaderRead() { errors = kLaterRound; }
-    void errorsExchanged() { errors = kNone; }
-};
-
-// One Create on the device frontier: what its steps share, and the steps.  run() is the build; a failure goes through
-// leaveAfterFailure().  Every step returns a status, FR_LAUNCH and HPSDF_HIP return from the step they are used in.
-struct FrontierBuild {
-    hpsdf_ctx* const ctx;
-    FrontierWorkspace* const ws;
-    const hpsdf_config cfg;  // (the copy that goes into the block)
-    const hpsdf_field* const field;
-    void** const block;
-    size_t* const size;
-    hpsdf_build_stats* const stats;
-    const int rank, world;
-    const hpsdf_allgather_fn gather;
-    void* const gatherUser;
-    const bool trace;
-    const double t0;
-    // what follows from the arguments
-    const hipStream_t s;
-    const uint32_t Kj;
-    // (replica: on several ranks a weighted incremental fit needs the node's previous rows, which another rank may have fitted: the
-    // arenas are replicas of each other then -- FrDev::replica)
-    const bool weighted, replica, mesh, splitMode;
-    const uint32_t stride0, strideK;  // doubles per rank in errs, round 0 and later (at most K jobs: smaller parts to all-gather than round 0's 4096)
-    const std::vector<size_t>& fitLds;
-    FrDev& d;
-    const FrTemplate& T;
-    const FrHdr* const hh;
-    uint32_t inlineNodes = kFrInlineNodes;  // trees up to here are selected by the closing launch itself, larger ones on the grid
-    FieldDev fd;
-    RootMap rm;
-#ifdef HPSDF_TEST_HOOKS  // (lib/libhpsdf_hooks.so, built for tests/: the production library does not look at the variable)
-    const char* const injected = std::getenv("HPSDF_TEST_FAIL_RANK");  // "<rank>:<round>"
-#else
-    static constexpr const char* injected = nullptr;  // (the statements that look at it fold away: the production library holds no trace of the hook)
-#endif
-    PendingExchange pending;
-    // round 0's plan: this rank's share when there are several
-    FrTemplate T0{};
-    const FitTask* r0Tasks = nullptr;
-    const FitBlock* r0Blocks = nullptr;
-    const uint64_t* r0JobP = nullptr;
-    size_t r0Lds = 0;
-    uint64_t part0 = 0;  // replica: doubles per rank in round 0's part of the arena
-    // the rounds
-    int rounds = 0;  // rounds the host has seen closed
-    uint32_t knownNodes = 0, knownMaxDeg = 2;
-    uint64_t knownArena = 0;
-    bool splitOpen = false, samplesTooLarge = false;  // of the round that the next closing launch opens (prepareNext)
-    uint64_t measuredLimit = 0;  // (hpsdf_ctx_set_build_limits' default, measured at most once per Create: checkBuildLimits)
-    // the round being closed, from closeRoundAndOpenNext to launchOpenedRound
-    bool pre = false, blind = false, splitCur = false, tooLargeCur = false;
-    int32_t splitFitCur = 0;
-    uint8_t* early = nullptr;  // the block of a build that stops after round 0, begun before the device has finished
-    bool earlyCopied = false;  // ... its coefficients are in it
-    double tSync = 0, tWeights = 0;
-
-    FrontierBuild(hpsdf_ctx* ctx, FrontierWorkspace* ws, const hpsdf_config* cfgIn, const hpsdf_field* field, uint64_t K, void** block, size_t* size,
-                  hpsdf_build_stats* stats, int rank, int world, hpsdf_allgather_fn gather, void* gatherUser, bool trace, double t0)
-        : ctx(ctx), ws(ws), cfg(configWithZeroedPads(cfgIn)), field(field), block(block), size(size), stats(stats), rank(rank), world(world),
-          gather(gather), gatherUser(gatherUser), trace(trace), t0(t0), s(ctx->stream), Kj((uint32_t)(K ? K : HPSDF_DEFAULT_JOBS_PER_ROUND)),
-          weighted(cfg.weighting_type != 0), replica(weighted && world > 1), mesh(innermost(field)->kind == kHostMesh),
-          splitMode(ctx->fitMode == HPSDF_FIT_SPLIT && !weighted), stride0(kFrJobs * HPSDF_JOB_HEADER_DOUBLES + kFrStatusPad),
-          strideK(Kj * HPSDF_JOB_HEADER_DOUBLES + kFrStatusPad), fitLds(fitLdsTable(weighted)), d(ws->d), T(ws->tmpl), hh(ws->hostHdr) {}
-    FrontierBuild(const FrontierBuild&) = delete;
-    ~FrontierBuild() { ctx->freeBlock(early); }
-
-    int run();
-    int leaveAfterFailure(int rc);
-
-    // the steps of run(), in its order
-    int planRound0();
-    int runRound0();
-    int closeRoundAndOpenNext();
-    void copyEarlyBlockWhileDeviceWorks();
-    int checkClosedRound();
-    int finishAfterRound0();
-    int selectOnGrid();
-    int launchOpenedRound();
-    int storeBlock();
-    // what the steps share
-    int exchange(void* dBuf, size_t bytesPerRank, const char* what);
-    int applyWeights(const FitBlock* blocks, uint32_t maxBlocks, size_t lds, const FitTask* tasks, const uint32_t* dCount, bool round0, uint32_t base, uint32_t nMine);
-    int prepareNext(uint32_t knownNodes, uint64_t knownArena, uint32_t knownMaxDeg, int roundsDone);
-    int launchRoundFits(uint32_t knownMaxDeg, bool splitRound);
-    int waitForRound(uint32_t want);
-    void rearmForNextBuild(bool wentOn);
-    FrDev initDev() const {  // what fr_init_kernel sees: the arrays as they are now, round 0's stride (where this rank's status for round 0's exchange lies)
-        FrDev di = d;
-        di.errStride = stride0;
-        return di;
-    }
-    bool injectedFailure(int round) const {
-        return injected && world > 1 && std::atoi(injected) == rank && std::strchr(injected, ':') && std::atoi(std::strchr(injected, ':') + 1) == round;
-    }
-};
-
-int FrontierBuild::run() {
-    // what every launch of this build is told (FrDev)
-    d.K = Kj;
-    d.rank = rank, d.world = world;
-    d.weighted = weighted ? 1 : 0;
-    d.replica = replica ? 1 : 0;
-    d.fastFit = (ctx->fitMode == HPSDF_FIT_FAST && field->kind != kHostTreeCsg && !weighted) ? 1 : 0;
-    d.splitFit = 0;
-    d.errStride = stride0, d.errStrideNext = strideK;
-    if (replica) {  // round 0's part of the arena, before anything can fail (PendingExchange)
-        uint32_t ends[9];
-        round0SliceEnds(T.nLeaves, world, ends);
-        pending.rowsAt(0, (size_t)round0PartRows(ends, world) * sizeof(double));
-    }
-    int rc;
-    if (world > 1) pending.round0Begins(stride0);
-    if ((rc = makeFieldDev(ctx, field, nullptr, &fd))) return rc;
-    if (injectedFailure(0)) return fail(HPSDF_ERR_OUT_OF_MEMORY, kInjectedFailureMsg);
-    for (int a = 0; a < 3; ++a) {
-        rm.bounds[a] = (double)(cfg.root_max[a] - cfg.root_min[a]);          // Octree.cpp:324
-        rm.centre[a] = (double)((cfg.root_min[a] + cfg.root_max[a]) / 2.0f);  // Octree.cpp:322
-    }
-    if ((rc = planRound0())) return rc;
-    if (const char* e = std::getenv("HPSDF_FRONTIER_INLINE_NODES")) inlineNodes = (uint32_t)std::strtoul(e, nullptr, 10);  // tests: 0 sends every round through the grid selection
-    d.buildStamp = ++ws->buildStamp ? ws->buildStamp : ++ws->buildStamp;  // (never 0)
-    d.stamps = trace ? 1u : 0u;
-    ws->hostHdr->round = 0, ws->hostHdr->done = 0;  // (the mirror still shows the previous build's last round: the waits below watch it)
-    if ((rc = runRound0())) return rc;
-    knownNodes = T.nNodes, knownMaxDeg = 2, knownArena = T0.arenaRows;
-    for (;;) {
-        if ((rc = closeRoundAndOpenNext())) return rc;
-        if (rounds == 0 && world == 1) copyEarlyBlockWhileDeviceWorks();
-        if ((rc = waitForRound((uint32_t)rounds + 1u))) return rc;
-        ++rounds;
-        if ((rc = checkClosedRound())) return rc;
-        if (rounds == 1 && world == 1 && hh->done && early && hh->nCoeffs == T.arenaRows && hh->nNodes == T.nNodes) return finishAfterRound0();
-        ctx->freeBlock(early);
-        early = nullptr;
-        if (hh->done) break;
-        // (as builderSelect: a total that is NaN or infinite never falls below the threshold -- the field is not finite somewhere)
-        if (!(std::fabs(hh->total) <= DBL_MAX))
-            return fail(HPSDF_ERR_INVALID_ARGUMENT, "the field is not a finite number at some sample point (the build's total error is NaN or infinite)");
-        knownNodes = hh->nNodes, knownMaxDeg = hh->maxDegree, knownArena = hh->arenaUsed;
-        if (world > 1) pending.afterHeaderRead();
-        // (replica: the round's rows are exchanged too -- from here on a rank that fails enters that exchange as well.  With the grid
-        // selection the part is known only when the batch kernel has run: selectOnGrid)
-        if (replica && pre) pending.rowsAt(hh->roundBase, (size_t)hh->partStride * sizeof(double));
-        if (!pre && (rc = selectOnGrid())) return rc;
-        if ((rc = launchOpenedRound())) return rc;
-    }
-    return storeBlock();
+hipError_t frLaunchWeigh(hipStream_t stream, const FrDev& d, uint32_t stride, uint32_t base, uint32_t jobs) {  // an error slot a lane, nine a job
+    hipLaunchKernelGGL(fr_weigh_kernel, dim3((std::max(1u, jobs) * 9u + 255u) / 256u), dim3(256), 0, stream, d, stride, base, jobs * 9u);
+    return hipGetLastError();
 }
-
-// in place: rank r's part at r * bytesPerRank
-int FrontierBuild::exchange(void* dBuf, size_t bytesPerRank, const char* what) {
-    if (world == 1) return HPSDF_OK;
-    const int grc = gather(gatherUser, dBuf, bytesPerRank, (void*)s);
-    if (grc != 0) return fail(HPSDF_ERR_STATE, std::string("the all-gather callback failed (") + what + ")");
-    return HPSDF_OK;
-}
-
-// Round 0 is every cell of the uniformly refined tree, straight from the template: this rank's share of it, and the cached upload
-// of the share's lists.
-int FrontierBuild::planRound0() {
-    T0 = T;
-    r0Tasks = ws->tmplTasks;
-    r0Blocks = ws->tmplBlocks;
-    r0JobP = ws->tmplJobP;
-    r0Lds = ws->tmplLds;
-    round0SliceEnds(T.nLeaves, world, T0.sliceFirst);
-    if (world > 1) {
-        const uint32_t first = T0.sliceFirst[rank], count = T0.sliceFirst[rank + 1] - first;
-        int g = 1, pl = 1;
-        frShape(2, false, std::max(1u, count), &g, &pl);
-        const uint32_t nBl = (count + (uint32_t)g - 1u) / (uint32_t)g;
-        // (replica: rank r's cells at r x part0 -- equal parts for the in-place all-gather -- and every cell's place known everywhere)
-        part0 = round0PartRows(T0.sliceFirst, world);
-        // this rank's task list, workgroup list and job -> arena map of round 0 depend on (rank, world, error stride, replica) alone:
-        // built and uploaded once, kept on the device for the Creates that follow (no upload, no wait per Create)
-        if (ws->r0Rank != rank || ws->r0World != world || ws->r0ErrStride != ws->d.errStride || ws->r0Replica != replica) {
-            std::vector<FitTask>& tk = ws->hostR0Tasks;
-            tk.assign(ws->hostTmplTasks.begin() + first, ws->hostTmplTasks.begin() + first + count);
-            std::vector<uint64_t> jobP(T.nLeaves, ~0ull & kOffMask);
-            for (uint32_t q = 0; q < count; ++q) {
-                tk[q].outOff = (replica ? (uint64_t)rank * part0 : 0ull) + (uint64_t)q * frCoef(2);
-                tk[q].sampleOff = (uint64_t)q * 729;
-                tk[q].errSlot = (uint32_t)rank * ws->d.errStride + q * HPSDF_JOB_HEADER_DOUBLES;
-                jobP[first + q] = tk[q].outOff;
-            }
-            if (replica)
-                for (int r = 0; r < world; ++r)
-                    for (uint32_t j = T0.sliceFirst[r]; j < T0.sliceFirst[r + 1]; ++j) jobP[j] = (uint64_t)r * part0 + (uint64_t)(j - T0.sliceFirst[r]) * frCoef(2);
-            std::vector<FitBlock> bl(nBl);
-            for (uint32_t k = 0; k < bl.size(); ++k) {
-                FitBlock& fb = bl[k];
-                std::memset(&fb, 0, sizeof fb);
-                fb.firstTask = k * (uint32_t)g;
-                fb.nTasks = (uint16_t)std::min<uint32_t>((uint32_t)g, count - k * (uint32_t)g);
-                fb.degree = 2;
-                fb.planesPerChunk = (uint8_t)pl;
-                fb.rowStart = 0, fb.rowEnd = (uint16_t)frCoef(2);
-                fb.depth = ws->hostTmplTasks[0].depth;
-            }
-            ws->r0Rank = ws->r0World = -1;
-            HPSDF_HIP(hipMemcpyAsync(ws->r0Tasks, tk.data(), count * sizeof(FitTask), hipMemcpyHostToDevice, s));
-            HPSDF_HIP(hipMemcpyAsync(ws->r0Blocks, bl.data(), bl.size() * sizeof(FitBlock), hipMemcpyHostToDevice, s));
-            HPSDF_HIP(hipMemcpyAsync(ws->r0JobP, jobP.data(), jobP.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            HPSDF_HIP(hipStreamSynchronize(s));  // (pageable sources)
-            ws->r0Rank = rank, ws->r0World = world, ws->r0ErrStride = ws->d.errStride, ws->r0Replica = replica;
-        }
-        r0Tasks = ws->r0Tasks, r0Blocks = ws->r0Blocks, r0JobP = ws->r0JobP;
-        r0Lds = frLds(2, g, pl);
-        T0.nTasks = count, T0.nBlocks = nBl;
-        T0.arenaRows = replica ? (uint64_t)world * part0 : (uint64_t)count * frCoef(2), T0.samples = (uint64_t)count * 729;
-    }
-    return HPSDF_OK;
-}
-
-// fr_round_kernel closes round r and opens round r + 1 in one launch, so what round r + 1 can need -- nodes for round r's
-// splits, arena rows and sample slots for round r + 1's fits -- is bounded from what the host knows when it launches it: the tree
-// after round r - 1 (whose largest degree can have risen by one since).  Also decides whether round r + 1's from-scratch fits
-// are split (ctx->fitMode): they are unless the sample buffer they hand their field values over in cannot be had.
-int FrontierBuild::prepareNext(uint32_t knownNodes, uint64_t knownArena, uint32_t knownMaxDeg, int roundsDone) {
-    const int degBound = (int)std::min<uint32_t>(knownMaxDeg + 1u, kMaxDegree);
-    const uint64_t needNodes = (uint64_t)knownNodes + 8ull * Kj;
-    const uint64_t needArena = knownArena + (replica ? (uint64_t)world * ((uint64_t)Kj * rowsPerJob(degBound) + 16) : (uint64_t)Kj * rowsPerJob(degBound));
-    {   // hpsdf_ctx_set_build_limits: the round about to open against the context's bounds -- before anything is allocated for it, so
-        // that a runaway build ends here with its statistics in the message instead of minutes later in a failed hipMalloc
-        // (a mesh build cannot do without its sample buffer; the hand-over buffer of split fits -- at most 2^31 samples, 16 GiB, whatever
-        // the tree's size -- is not part of what grows without bound and is not counted: counting it would make the two schedulers'
-        // split decisions depend on the limit, and they promise the same bytes)
-        const uint64_t needSamples = mesh ? std::min<uint64_t>((uint64_t)Kj * samplesPerJob(degBound), 1ull << 31) : 0ull;
-        const uint64_t bytes = needNodes * FrontierWorkspace::kBytesPerNode + (needArena + needSamples) * sizeof(double);
-        const uint64_t held = (uint64_t)ws->nodeCap * FrontierWorkspace::kBytesPerNode + (ws->arenaCap + ws->sampleCap) * sizeof(double);
-        const uint64_t growBytes = needNodes * FrontierWorkspace::kBytesPerNode + needArena * sizeof(double);  // (the default limit's subject)
-        const int lrc = checkBuildLimits(ctx, knownNodes, bytes, growBytes, held, &measuredLimit, (uint64_t)roundsDone, roundsDone ? hh->total : 8.0 * 8.0 * 8.0 * 8.0 * HPSDF_INITIAL_NODE_ERR,
-                                         cfg.target_error_threshold);
-        if (lrc) return lrc;
-    }
-    if (needNodes > 0xFFFFFFF0ull) return fail(HPSDF_ERR_BUILD_LIMIT, "build limit: the device-side frontier indexes nodes with 32 bits");
-    hipError_t e = ws->ensureNodes((uint32_t)needNodes, s);
-    if (e == hipSuccess) e = ws->ensureArena(needArena, knownArena, s);
-    if (e != hipSuccess) return hipFail(e, "frontier buffers");
-    splitOpen = splitMode && degBound >= ctx->splitMinDegree;
-    samplesTooLarge = false;
-    if (mesh || splitOpen) {
-        // (the round's own count decides on the device whether it splits -- the host scheduler's rule, FrHdr::splitRound; the host
-        // provides for what the round can need, up to the 2^31 samples a split round may have)
-        uint64_t need = (uint64_t)Kj * samplesPerJob(degBound);
-        if (need > (1ull << 31)) {
-            if (mesh) samplesTooLarge = true;  // (a mesh build fails when that round comes)
-            need = 1ull << 31;
-        }
-        if (!samplesTooLarge && (e = ws->ensureSamples(need, s)) != hipSuccess) {
-            if (mesh) return hipFail(e, "frontier sample buffer");
-            (void)hipGetLastError();  // no room for the hand-over buffer: the exact fit needs none
-            splitOpen = false;
-        }
-    }
-    d.sampleCap = ws->sampleCap;
-    return HPSDF_OK;
-}
-
-// Weighted builds, once per round behind the fits: |mean FApprox| of every fit (fit_weight_kernel, straight into pinned
-// host memory) -> the weight, with the HOST's pow / exp (Octree.cpp:1224-1226, :1246: the libm the oracle and the host
-// scheduler call; a device pow would have to match it bit for bit) -> error * weight on the device (:1078-1086).
-// Everything else of the round -- selection, tasks, decision, bookkeeping, packing -- stays where it is.
-// (base, nMine: this rank's run of error slots and its jobs of the round)
-int FrontierBuild::applyWeights(const FitBlock* blocks, uint32_t maxBlocks, size_t lds, const FitTask* tasks, const uint32_t* dCount, bool round0, uint32_t base,
-                                uint32_t nMine) {
-    HPSDF_HIP(launchFitWeight(s, blocks, maxBlocks, lds, tasks, ws->arena, d.means, ctx->dTables, dCount));
-    const uint32_t stamp = ++ws->flagStamp;
-    FR_LAUNCH(fr_means_done_kernel, dim3(1), dim3(64), s, d, stamp);
-    const double ts = frNow();
-    {
-        const volatile uint32_t* flag = ws->hostFlag;
-        if (!watchWord(&flag[1], stamp, 2.0e3)) HPSDF_HIP(hipStreamSynchronize(s));
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (flag[1] != stamp) return fail(HPSDF_ERR_STATE, "frontier: the round's means did not arrive");
-    }
-    const double tw = frNow();
-    tSync += tw - ts;
-    const uint32_t nJobs = world == 1 ? std::min<uint32_t>(ws->hostFlag[0], kFrJobs) : std::min<uint32_t>(nMine, kFrJobs);
-    const double dd = std::sqrt(3.0), strength = cfg.weighting_strength;
-    const double* mean = ws->hostMeans + base;
-    double* w = ws->hostWeights + base;
-    const uint32_t step = round0 ? 9u : 1u;  // round 0: every job is a coarse cell with one fit (slot 0 of its nine)
-    for (uint32_t i = 0; i < nJobs * 9u; i += step) {
-        if (cfg.weighting_type == 1) {
-            const double k = std::pow(1.0 - mean[i] / dd, strength);
-            w[i] = std::min<double>(1.0, std::max<double>(k, 0.0));
-        } else {
-            w[i] = std::exp(-1.0 * strength * mean[i] / dd);
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_release);
-    tWeights += frNow() - tw;
-    FR_LAUNCH(fr_weigh_kernel, dim3((std::max(1u, nJobs) * 9u + 255u) / 256u), dim3(256), s, d, round0 ? 1u : 9u, base, nJobs * 9u);
-    return HPSDF_OK;
-}
-
-// a round's fits, from the lists the device wrote (fit_mesh.hip, fit.hip; grids are upper bounds)
-int FrontierBuild::launchRoundFits(uint32_t knownMaxDeg, bool splitRound) {
-    const int degHi = (int)std::min<uint32_t>(kMaxDegree - 1, knownMaxDeg + 1);
-    const uint32_t taskBound = 9u * Kj;
-    bool degHiDone = false;
-    FieldDev fdr = fd;
-    if (mesh) {
-        for (int deg = 2; deg <= degHi; ++deg)
-            HPSDF_HIP(launchMeshSampleRange(s, d.tasks, &d.hdr->degTasks[deg][0], std::min<uint32_t>(taskBound, 65535u), deg, ctx->dTables, fd,
-                                            rm, ws->samples));
-        fdr.kind = kFieldSamples;
-        fdr.samples = ws->samples;
-    } else if (splitRound) {
-        fdr.samples = ws->samples;  // (the exact kernel writes the field values of split fits there)
-    }
-    // One launch for every degree of the round (fit_kernels.hpp fit_multi_kernel); the matrix-core fit and
-    // HPSDF_FRONTIER_SPLIT_FITS=1 keep one launch per degree, side by side on three streams.
-    static const bool splitFits = std::getenv("HPSDF_FRONTIER_SPLIT_FITS") != nullptr;
-    if (!d.fastFit && !splitFits) {
-        size_t lds = 0;
-        for (int deg = 2; deg <= degHi; ++deg) lds = std::max(lds, fitLds[deg]);
-        HPSDF_HIP(launchFitMulti(s, d.blocks, taskBound, lds, d.tasks, ws->arena, d.errs, ctx->dTables, fdr, rm, &d.hdr->nBlocks));
-        degHiDone = true;
-    }
-    const bool fork = !degHiDone && degHi > 2 && std::getenv("HPSDF_FRONTIER_ONE_STREAM") == nullptr;
-    if (fork) HPSDF_HIP(hipEventRecord(ws->forkEv, s));
-    bool used[FrontierWorkspace::kSide] = {false, false, false};
-    for (int deg = 2; deg <= degHi && !degHiDone; ++deg) {
-        hipStream_t fs = s;
-        if (fork && deg > 2) {
-            const int k = (deg - 3) % FrontierWorkspace::kSide;
-            fs = ws->side[k];
-            if (!used[k]) HPSDF_HIP(hipStreamWaitEvent(fs, ws->forkEv, 0));
-            used[k] = true;
-        }
-        if (d.fastFit && deg >= 4 && deg <= 11)
-            HPSDF_HIP(launchFitMfma(fs, deg, d.blocks, taskBound, d.tasks, ws->arena, d.errs, ctx->dTables, fdr, rm, &d.hdr->degBlocks[deg][0]));
-        else
-            HPSDF_HIP(launchFit(fs, deg <= 8 ? deg : 0, 1, d.blocks, taskBound, fitLds[deg], d.tasks, ws->arena, d.errs, nullptr,
-                                ctx->dTables, fdr, rm, &d.hdr->degBlocks[deg][0]));
-    }
-    for (int k = 0; k < FrontierWorkspace::kSide; ++k)
-        if (used[k]) {
-            HPSDF_HIP(hipEventRecord(ws->joinEv[k], ws->side[k]));
-            HPSDF_HIP(hipStreamWaitEvent(s, ws->joinEv[k], 0));
-        }
-    if (splitRound)  // the rows below the top degree of the split fits, from the samples the exact kernel left (H children: degree <= knownMaxDeg)
-        for (int deg = std::max(2, ctx->splitMinDegree); deg <= (int)std::min<uint32_t>(knownMaxDeg, 11u); ++deg)
-            HPSDF_HIP(launchFitMfmaLow(s, deg, d.tasks, &d.hdr->lowTasks[deg][0], 0u, 0u, 8u * Kj, ws->arena, ctx->dTables, ws->samples, rm, fd.leftAssoc));
-    if (weighted) {
-        size_t lds = 0;
-        for (int deg = 2; deg <= degHi; ++deg) lds = std::max(lds, fitLds[deg]);
-        int rcw;
-        const uint32_t mine = world == 1 ? 0u : hh->sliceFirst[rank + 1] - hh->sliceFirst[rank];  // (one rank: the device says how many)
-        if ((rcw = applyWeights(d.blocks, taskBound, lds, d.tasks, &d.hdr->nBlocks, false, world == 1 ? 0u : (uint32_t)rank * strideK, mine))) return rcw;
-    }
-    return HPSDF_OK;
-}
-
-// The round is over for the host when the header's mirror shows the next round number: the closing workgroup writes it into
-// pinned memory behind a system-scope fence.
-int FrontierBuild::waitForRound(uint32_t want) {
-    const double ts = frNow();
-    const volatile uint32_t* roundWord = &hh->round;
-    if (!watchWord(roundWord, want, 2.0e3)) {  // two milliseconds of watching, then the ordinary wait
-        HPSDF_HIP(hipStreamSynchronize(s));
-        if (*roundWord != want) {
-            // The stream is idle and the mirror still shows the old round: the pinned mirror is not coherent on this system.
-            // Fetch the header itself and let it decide.
-            HPSDF_HIP(hipMemcpy(ws->hostHdr, d.hdr, kFrHdrCopyBytes, hipMemcpyDeviceToHost));
-            if (hh->round != want) return fail(HPSDF_ERR_STATE, "frontier: a round ended without advancing");
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    tSync += frNow() - ts;
-    return HPSDF_OK;
-}
-
-// the launch that leaves the workspace ready for this context's next build (FrontierWorkspace::clean)
-void FrontierBuild::rearmForNextBuild(bool wentOn) {
-    hipLaunchKernelGGL(fr_init_kernel, dim3((T.nNodes + 255) / 256), dim3(256), 0, s, initDev(), T0);
-    ws->clean = hipGetLastError() == hipSuccess, ws->cleanRank = rank, ws->cleanWorld = world;
-    ws->lastWentOn = wentOn;
-}
-
-int FrontierBuild::runRound0() {
-    int rc;
-    hipError_t e = ws->ensureArena(std::max<uint64_t>(1, T0.arenaRows), 0, s);
-    if (e == hipSuccess && mesh) e = ws->ensureSamples(std::max<uint64_t>(1, T0.samples), s);
-    if (e != hipSuccess) return hipFail(e, "frontier buffers");
-    if ((rc = prepareNext(T.nNodes, T0.arenaRows, 2u, 0))) return rc;
-    d.target = cfg.target_error_threshold;
-    if (!ws->clean || ws->cleanRank != rank || ws->cleanWorld != world) FR_LAUNCH(fr_init_kernel, dim3((T.nNodes + 255) / 256), dim3(256), s, initDev(), T0);
-    ws->clean = false;
-    FieldDev fdr = fd;
-    if (mesh) {
-        HPSDF_HIP(launchMeshSample(s, r0Tasks, T0.nTasks, 2, ctx->dTables, fd, rm, ws->samples));
-        fdr.kind = kFieldSamples;
-        fdr.samples = ws->samples;
-    }
-    // (one rank: the rows also go straight into pinned host memory -- if the build stops after this round they are its packed store)
-    HPSDF_HIP(launchFit(s, 2, 1, r0Blocks, T0.nBlocks, r0Lds, r0Tasks, ws->arena, d.errs, world == 1 ? ws->pinnedDev : nullptr, ctx->dTables, fdr, rm));
-    if (weighted && (rc = applyWeights(r0Blocks, T0.nBlocks, r0Lds, r0Tasks, nullptr, true, world == 1 ? 0u : (uint32_t)rank * stride0,
-                                       T0.sliceFirst[rank + 1] - T0.sliceFirst[rank])))
-        return rc;
-    if (replica) {
-        if (pending.rowsBytes != (size_t)part0 * sizeof(double)) return fail(HPSDF_ERR_STATE, "frontier: round 0's part of the arena");
-        pending.rowsEntered();
-        if ((rc = exchange(ws->arena, pending.rowsBytes, "round 0's rows"))) return rc;
-    }
-    if ((rc = exchange(d.errs, (size_t)stride0 * sizeof(double), "round 0"))) return rc;
-    pending.afterRound0Exchanges(strideK);
-    d.errStride = strideK;  // (of the exchange that comes next: where a failing rank leaves its status)
-    return HPSDF_OK;
-}
-
-// close round `rounds`, open the next
-int FrontierBuild::closeRoundAndOpenNext() {
-    int rc;
-    pre = (uint64_t)knownNodes + 8ull * Kj <= inlineNodes;
-    splitCur = splitOpen, tooLargeCur = samplesTooLarge;
-    FrDev dk = d;
-    dk.splitFit = splitFitCur = splitCur ? std::max(2, ctx->splitMinDegree) : 0;
-    if (rounds == 0) {
-        dk.batchIdx = ws->tmplLeaves, dk.batchErr = ws->tmplErr, dk.jobP = r0JobP, dk.jobH = r0JobP;
-        dk.errStride = stride0;
-    }
-    FR_LAUNCH(fr_round_kernel, dim3(2 + ((rounds == 0 ? T.nLeaves : Kj) + 127u) / 128u), dim3(1024), s, dk, (pre ? 1 : 0) | (ws->lastWentOn && pre ? 2 : 0));
-    // From the second round on the fits are launched without waiting for the header (one rank, no host step in between): what they
-    // need to know is on the device -- their lists and counts -- and a build that has stopped leaves them nothing to do.  The
-    // largest degree may have risen once more than the host knows.
-    const bool noBlind = std::getenv("HPSDF_FRONTIER_NO_BLIND") != nullptr;  // (tests, comparisons)
-    // Behind round 0 too when this context's last build went on past it (the guess that also hands round 0's total to the last
-    // workgroup): the second round's fits then start when the closing launch ends instead of a host round trip later (~15 us); a
-    // build that does stop there leaves two empty launches behind.
-    blind = (rounds >= 1 || ws->lastWentOn) && pre && world == 1 && !weighted && !frSyncEveryLaunch() && !noBlind;
-    if (blind) {
-        if (mesh && tooLargeCur) return fail(HPSDF_ERR_UNSUPPORTED, "round too large for the sampled mesh path");
-        d.splitFit = splitFitCur;
-        FrDev de = d;  // (not dk: round 0's closing launch reads the template's batch, the lists are written for the next one)
-        FR_LAUNCH(fr_emit_kernel, dim3((Kj + 127u) / 128u), dim3(1024), s, de);
-        if ((rc = launchRoundFits(std::min<uint32_t>(knownMaxDeg + 1u, kMaxDegree), splitCur))) return rc;
-    }
-    return HPSDF_OK;
-}
-
-// One rank, round 0: a build that stops here has its packed store in pinned memory already (the fit wrote it there too), and
-// everything else of its block is known in advance: write that part while the device works
-void FrontierBuild::copyEarlyBlockWhileDeviceWorks() {
-    const uint64_t nc0 = T.arenaRows, nn0 = T.nNodes;
-    early = (uint8_t*)ctx->allocBlock(blockBytes(nc0, nn0));
-    if (!early) return;
-    std::memcpy(early, &nc0, 8);
-    std::memcpy(early + blockNodeCountAt(nc0), &nn0, 8);
-    std::memcpy(early + blockNodesAt(nc0), ws->hostNodesAfterRound0.data(), sizeof(hpsdf_node) * (size_t)nn0);
-    std::memcpy(early + blockConfigAt(nc0, nn0), &cfg, sizeof cfg);
-    // ... and the rows themselves as soon as the closing launch says that the fit before it has finished -- long before it
-    // can say whether the build stops here (the running total is 4096 dependent additions away): 320 KB out of memory the
-    // GPU has just written take a core ~20 us, which now pass while the device works.  In pieces, with an eye on the round
-    // word: a build that goes on must not wait for a copy it will not use.  (Two words under one limit: not watchWord.)
-    const volatile uint32_t* landed = &hh->landed;
-    const volatile uint32_t* roundWord = &hh->round;
-    const double limit = frNow() + 2.0e3;
-    while (*landed != d.buildStamp && *roundWord == 0 && frNow() < limit) frCpuRelax();
-    if (*landed == d.buildStamp) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const size_t total = 8 * (size_t)nc0, piece = 32768;
-        size_t at = 0;
-        for (; at < total && (*roundWord == 0 || *(const volatile uint32_t*)&hh->done); at += piece) std::memcpy(early + kBlockCoeffsAt + at, ws->pinned + at, std::min(piece, total - at));
-        earlyCopied = at >= total;
-    }
-}
-
-// what the header says about the round that has just closed
-int FrontierBuild::checkClosedRound() {
-    if (world > 1 && hh->rPad)
-        return fail(HPSDF_ERR_STATE, "rank " + std::to_string(hh->rPad - 1) + " failed in round " + std::to_string(rounds - 1) + ": its own error was returned there");
-    if (hh->overflow & 1u) return fail(HPSDF_ERR_STATE, "frontier: node capacity exceeded");
-    if (hh->overflow & 4u) return fail(HPSDF_ERR_STATE, "frontier: a workgroup of the round's kernel did not arrive");
-    if (trace) {
-        std::fprintf(stderr, "[frontier round %d] lead (cycles): wait-all %lld close %lld", rounds - 1, (long long)(hh->dbg[10] - hh->dbg[9]),
-                     (long long)(hh->dbg[11] - hh->dbg[10]));
-        if (!hh->done && pre) {
-            std::fprintf(stderr, " | select %lld batch", (long long)(hh->dbg[0] - hh->dbg[11]));
-            for (int k = 1; k <= 8; ++k) std::fprintf(stderr, " %lld", (long long)(hh->dbg[k] - hh->dbg[k - 1]));
-            std::fprintf(stderr, " | total+commit %lld", (long long)(hh->dbg[12] - hh->dbg[8]));
-        }
-        std::fprintf(stderr, " | chain %lld (first operands %lld, first 2048 additions %lld)", (long long)(hh->dbg[14] - hh->dbg[13]), (long long)(hh->dbg[15] - hh->dbg[13]),
-                     (long long)(hh->dbg[16] - hh->dbg[15]));
-        std::fprintf(stderr, "\n");
-    }
-    return HPSDF_OK;
-}
-
-// the build stopped after round 0 and the block begun early is its block
-int FrontierBuild::finishAfterRound0() {
-    if (!earlyCopied) std::memcpy(early + kBlockCoeffsAt, ws->pinned, 8 * (size_t)T.arenaRows);
-    rearmForNextBuild(false);
-    *block = early;
-    *size = blockBytes(T.arenaRows, T.nNodes);
-    early = nullptr;
-    if (stats) fillStats(hh, hh->nNodes, hh->nCoeffs, ctx->fitMode, stats);
-    if (trace) std::fprintf(stderr, "[frontierCreate] us: total %.0f (waiting for the device %.0f, stopped after round 0)\n", frNow() - t0, tSync);
-    return HPSDF_OK;
-}
-
-// a large tree: the selection as a grid, then batch and lists (the header's arenaUsed lags one round: launchOpenedRound bounds it)
-int FrontierBuild::selectOnGrid() {
-    FrDev dl = d;
-    dl.splitFit = splitFitCur;
-    FR_LAUNCH(fr_select_kernel, dim3(std::min<uint32_t>(512u, (knownNodes + 255u) / 256u)), dim3(256), s, dl);
-    FR_LAUNCH(fr_batch_kernel, dim3(1), dim3(1024), s, dl);
-    FR_LAUNCH(fr_tasks_kernel, dim3((16u * Kj + 255u) / 256u), dim3(256), s, dl);
-    if (replica) {
-        // Where the round's part of the arena lies is the batch kernel's decision, and the exchange below needs it.  The
-        // context's stream does not synchronise with the null stream (hipStreamNonBlocking): a plain hipMemcpy right behind the
-        // launches would fetch the PREVIOUS round's roundBase / partStride.  Wait for the three kernels, then fetch.
-        HPSDF_HIP(hipStreamSynchronize(s));
-        HPSDF_HIP(hipMemcpy(ws->hostHdr, d.hdr, kFrHdrCopyBytes, hipMemcpyDeviceToHost));
-        pending.rowsAt(hh->roundBase, (size_t)hh->partStride * sizeof(double));
-    }
-    return HPSDF_OK;
-}
-
-// The fits of the round that the closing launch opened, and their exchanges.
-// (A rank whose share fails from here on knows which exchanges the others are heading for, and how large their parts are: with
-// the grid selection that is only true once the batch kernel has spoken, hence the order.  A failed launch of the three
-// selection kernels themselves -- a lost device, not a full one -- is not covered: that rank enters the errors' exchange alone.)
-int FrontierBuild::launchOpenedRound() {
-    int rc;
-    if (injectedFailure(rounds)) return fail(HPSDF_ERR_OUT_OF_MEMORY, kInjectedFailureMsg);
-    if (mesh && tooLargeCur) return fail(HPSDF_ERR_UNSUPPORTED, "round too large for the sampled mesh path");
-    if (pre && !blind) {
-        FrDev de = d;
-        de.splitFit = splitFitCur;
-        FR_LAUNCH(fr_emit_kernel, dim3((Kj + 127u) / 128u), dim3(1024), s, de);
-    }
-    // capacities of the launch that closes this round; the arena may move: nothing that writes it is in flight
-    if ((rc = prepareNext(knownNodes, knownArena + (pre ? 0ull : (uint64_t)(replica ? world : 1) * ((uint64_t)Kj * rowsPerJob((int)knownMaxDeg) + 16)), knownMaxDeg, rounds))) return rc;
-    d.splitFit = splitFitCur;
-    if (!blind && (rc = launchRoundFits(knownMaxDeg, splitCur))) return rc;
-    if (replica) {
-        pending.rowsEntered();
-        if ((rc = exchange(ws->arena + pending.rowsOff, pending.rowsBytes, "a round's rows"))) return rc;  // (the arena may have moved: offset, not pointer)
-    }
-    if (frSyncEveryLaunch()) std::fprintf(stderr, "[frontier] fits of round %d ... %s\n", rounds, hipGetErrorString(hipStreamSynchronize(s)));
-    if ((rc = exchange(d.errs, (size_t)strideK * sizeof(double), "a round's errors"))) return rc;
-    pending.errorsExchanged();
-    return HPSDF_OK;
-}
-
-// ReallocCoeffs, and Octree::ToMemoryBlock (Octree.cpp:424-456: [u64 nCoeffs][f64 x nCoeffs][u64 nNodes][Node x nNodes][Config]): the
-// device writes coefficients and node array into pinned host memory (fr_store_kernel), the host moves each part into the block
-// when the mirror says it is there -- the node array while the coefficients are still landing
-int FrontierBuild::storeBlock() {
-    int rc;
-    const uint64_t nc = hh->nCoeffs, nn = hh->nNodes;
-    {
-        hipError_t e = ws->ensurePinned(8 * (size_t)nc + sizeof(hpsdf_node) * (size_t)nn);
-        if (e != hipSuccess) return hipFail(e, "block staging");
-        d.store = ws->pinnedDev;
-        FR_LAUNCH(fr_subtree_kernel, dim3(((uint32_t)nn + 255u) / 256u), dim3(256), s, d);
-        if (world > 1 && !replica) {
-            // the packed store from one all-gather of the ranks' pack buffers (each rank's own segments in node order)
-            FR_LAUNCH(fr_packpos_kernel, dim3(1), dim3(1024), s, d);
-            HPSDF_HIP(hipStreamSynchronize(s));
-            uint64_t stride = 1;
-            for (int r = 0; r < world; ++r) stride = std::max<uint64_t>(stride, hh->packCount[r]);
-            stride = (stride + 15) & ~15ull;
-            e = ws->ensurePack((uint64_t)world * stride, s);
-            if (e != hipSuccess) return hipFail(e, "pack buffers");
-            d.packStride = stride;
-            FR_LAUNCH(fr_pack_kernel, dim3(std::min<uint32_t>(2048u, (knownNodes + 3u) / 4u)), dim3(256), s, d);
-            if ((rc = exchange(d.pack, (size_t)stride * sizeof(double), "the packed coefficients"))) return rc;
-        }
-        FR_LAUNCH(fr_store_kernel, dim3(((uint32_t)nn + kStoreNodes - 1u) / kStoreNodes), dim3(256), s, d);
-    }
-    const size_t bytes = blockBytes(nc, nn);
-    uint8_t* p = (uint8_t*)ctx->allocBlock(bytes);
-    if (!p) {
-        (void)hipStreamSynchronize(s);
-        return fail(HPSDF_ERR_OUT_OF_MEMORY, "malloc of the memory block failed");
-    }
-    const double tc = frNow();
-    std::memcpy(p, &nc, 8);
-    std::memcpy(p + blockNodeCountAt(nc), &nn, 8);
-    std::memcpy(p + blockConfigAt(nc, nn), &cfg, sizeof cfg);
-    for (int part = 0; part < 2; ++part) {  // 0: the node array, 1: the coefficients
-        if (!watchWord(&hh->stored[part], d.buildStamp, 2.0e3)) {  // (two milliseconds of watching, then the ordinary wait: the launch has finished, its stores are there)
-            const hipError_t e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                ctx->freeBlock(p);
-                return hipFail(e, "block download");
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (part == 0)
-            std::memcpy(p + blockNodesAt(nc), ws->pinned + 8 * (size_t)nc, sizeof(hpsdf_node) * (size_t)nn);
-        else
-            std::memcpy(p + kBlockCoeffsAt, ws->pinned, 8 * (size_t)nc);
-    }
-    const double tcopy = frNow() - tc;
-    *block = p;
-    *size = bytes;
-    if (stats) fillStats(hh, nn, nc, ctx->fitMode, stats);
-    rearmForNextBuild(rounds > 1);
-    if (trace)
-        std::fprintf(stderr, "[frontierCreate] us: total %.0f (waiting for the device %.0f over %d rounds, weights on the host %.0f, block download %.0f)\n",
-                     frNow() - t0, tSync, rounds, tWeights, tcopy);
-    return HPSDF_OK;
-}
-
-// A build that failed.  Several ranks, with an exchange pending: this rank still enters it, then returns its own error text.
-int FrontierBuild::leaveAfterFailure(int rcBody) {
-    if (world > 1 && pending.errors != PendingExchange::kNone) {
-        const std::string own = hpsdf_last_error();
-        const size_t stride = pending.errStride;
-        const unsigned long long ones = ~0ull;
-        if (pending.rows) (void)gather(gatherUser, ws->arena + pending.rowsOff, pending.rowsBytes, (void*)s);  // (replica: the others exchange the round's rows first)
-        // (this rank's errors of the round were never written: zeros instead of whatever the buffer held -- the others' round kernels
-        // read every job's errors before their leader looks at the status)
-        if (hipMemsetAsync(ws->d.errs + (size_t)rank * stride, 0, stride * sizeof(double), s) == hipSuccess &&
-            hipMemcpyAsync(ws->d.errs + (size_t)rank * stride + (stride - 1), &ones, sizeof ones, hipMemcpyHostToDevice, s) == hipSuccess)
-            (void)gather(gatherUser, ws->d.errs, stride * sizeof(double), (void*)s);
-        (void)hipStreamSynchronize(s);
-        return fail(rcBody, own);
-    }
-    // A build that fails leaves nothing in flight: the round kernel's leader publishes the round number -- which is what the host
-    // watches -- BEFORE it prepares the next round, so a failure noticed right there (another rank's status, an overflow) would
-    // otherwise return with that kernel still writing the header's mirror and the lists, into buffers the caller may free next.
-    const std::string own = hpsdf_last_error();
-    (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    return fail(rcBody, own);
-}
-
-}  // namespace
-
-int frontierCreate(hpsdf_ctx* ctx, const hpsdf_config* cfgIn, const hpsdf_field* field, uint64_t K, void** block, size_t* size,
-                   hpsdf_build_stats* stats, int rank, int world, hpsdf_allgather_fn gather, void* gatherUser) {
-    if (world < 1 || world > 8 || rank < 0 || rank >= world) return fail(HPSDF_ERR_INVALID_ARGUMENT, "bad rank/world (1..8 ranks)");
-    if (world > 1 && !gather) return fail(HPSDF_ERR_INVALID_ARGUMENT, "a multi-rank build needs an all-gather");
-    const bool trace = std::getenv("HPSDF_TRACE") != nullptr;
-    const double t0 = frNow();
-    if (const int rc = validateBuildConfig(cfgIn)) return rc;
-    HPSDF_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    if (!ctx->frontierScratch) {
-        auto w = std::make_shared<FrontierWorkspace>();
-        const hipError_t e = w->init(ctx->device, s);
-        if (e != hipSuccess) return hipFail(e, "frontier workspace");
-        ctx->frontierScratch = w;
-    }
-    FrontierWorkspace* ws = static_cast<FrontierWorkspace*>(ctx->frontierScratch.get());
-    if (ws->inUse) return fail(HPSDF_ERR_STATE, "one Create at a time per context");
-    ws->inUse = true;
-    struct Release {
-        FrontierWorkspace* w;
-        ~Release() { w->inUse = false; }
-    } release{ws};
-    FrontierBuild b(ctx, ws, cfgIn, field, K, block, size, stats, rank, world, gather, gatherUser, trace, t0);
-    if (b.weighted) {
-        const hipError_t e = ws->ensureWeighting();
-        if (e != hipSuccess) return hipFail(e, "frontier weighting buffers");
-    }
-    {
-        const hipError_t e = ws->ensureRanks(world, s);
-        if (e != hipSuccess) return hipFail(e, "frontier buffers");
-    }
-    const int rc = b.run();
-    return rc ? b.leaveAfterFailure(rc) : rc;
+hipError_t frLaunchInit(hipStream_t stream, const FrDev& d, const FrTemplate& t) {  // a node of the template a lane
+    hipLaunchKernelGGL(fr_init_kernel, dim3((t.nNodes + 255) / 256), dim3(256), 0, stream, d, t);
+    return hipGetLastError();
 }
 
 }  // namespace hpsdf

@@ -1,6 +1,7 @@
-// Octree::Create with the frontier on the device (frontier.hip): what hpsdf_create runs for fields the GPU evaluates
-// itself (analytic primitives, meshes, tree-CSG of those) without nearness weighting and K <= 4096.  Everything else --
-// host callbacks, weighted builds, the stepwise hpsdf_build_* API -- runs the host scheduler of builder.cpp.
+// Octree::Create with the frontier on the device (kernels: frontier.hip, driver: frontier_build.cpp): what hpsdf_create runs
+// for fields the GPU evaluates itself (analytic primitives, meshes, tree-CSG of those) with K <= 4096, with or without nearness
+// weighting.  Everything else -- host callbacks, builds that log every job, meshes under the reference's face rule or
+// HPSDF_MESH_FUSED=1, anything under HPSDF_HOST_FRONTIER=1, the stepwise hpsdf_build_* API -- runs the host scheduler of builder.cpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>

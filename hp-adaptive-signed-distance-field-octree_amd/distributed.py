@@ -11,7 +11,7 @@ Create
 
     On GPUs the whole loop sits behind the C ABI (hpsdf_create_distributed) and this module only supplies
     the all-gather.  Fields the GPU evaluates itself (analytic, mesh, tree-CSG), with or without
-    nearness weighting, take the device-side frontier (csrc/frontier.hip) on up to 8 ranks: selection,
+    nearness weighting, take the device-side frontier (csrc/frontier.hip, frontier_build.cpp) on up to 8 ranks: selection,
     slicing, decision and bookkeeping run on every rank's GPU and the exchange points are all-gathers of
     device buffers.  A weighted build hands the rows each round fitted to every rank (one more
     all-gather per round, of the round's part of the arena: a weighted incremental fit copies the

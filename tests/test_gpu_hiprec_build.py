@@ -107,7 +107,7 @@ def _one_shot(H, contexts, monkeypatch, name, variant):
     spec, root, target, K = case_spec(name)
     cfg = H.make_config(target, *root)
     if K > 4096 and variant != "host":
-        # The device frontier carries rounds of up to 4096 jobs (kFrJobs, csrc/frontier.hip); a larger K goes to the host scheduler.
+        # The device frontier carries rounds of up to 4096 jobs (kFrJobs, csrc/frontier_dev.hpp); a larger K goes to the host scheduler.
         # cube-allK never queues more than 4096 entries, so K = 4096 selects what K = 8192 selects: the same replay serves both.
         K = 4096
     if variant.startswith("ranks"):

@@ -236,3 +236,16 @@ def test_production_library_holds_no_lab_or_fault_injection_code(H):
     hdr = open(os.path.join(ROOT, "include", "hpsdf.h")).read()
     assert int(re.search(r"#define HPSDF_ABI_VERSION (\d+)", hdr).group(1)) == H.ABI_VERSION
     assert C.sizeof(H.BuildStats) == 112  # frozen since ABI 3 (include/hpsdf.h)
+
+
+def test_hook_library_recompiles_exactly_the_units_that_hold_a_hook(H):
+    """libhpsdf_hooks.so compiles build.HOOK_SOURCES again under -DHPSDF_TEST_HOOKS and links every other production object: the list
+    must name exactly the compiled units whose text asks for the macro, or a hook that moves to another file silently leaves the
+    library (its tests would then inject nothing).  Every listed source exists."""
+    import importlib
+    build = importlib.import_module("hpsdf_amd.build")
+    for s in build.SOURCES + build.HOOK_SOURCES:
+        assert os.path.isfile(os.path.join(build.CSRC, s)), s
+    units = [f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp"))]  # (headers are compiled with the units that include them)
+    hooked = {s for s in units if "#ifdef HPSDF_TEST_HOOKS" in open(os.path.join(build.CSRC, s), errors="replace").read()}
+    assert hooked == set(build.HOOK_SOURCES) and len(build.HOOK_SOURCES) == len(hooked)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device-side frontier (csrc/frontier.hip) against the host scheduler (csrc/builder.cpp): same MemoryBlock byte for byte,
+"""Device-side frontier (kernels csrc/frontier.hip, driver csrc/frontier_build.cpp) against the host scheduler (csrc/builder.cpp): same MemoryBlock byte for byte,
 and the time of both.  usage: python tools/frontier_check.py [--mesh]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Disassembly of the built HIP objects' gfx950 code.
   python tools/kernel_isa.py <object stem, e.g. kernels> <mangled-name substring>     print the functions whose name matches
-  python tools/kernel_isa.py --compare <other build dir> [--diff]                      is every function's instruction stream the same?
+  python tools/kernel_isa.py --compare <other build dir> [--diff] [--rename OLD=NEW]... [--rename-file FILE]
+                                                                                       is every function's instruction stream the same?
 --compare: every kernel and every non-inlined device function of build/*.hip.o against those of another tree's build directory, by
 mangled name across ALL objects (so code may move between translation units; a helper that is not inlined may sit in several
 objects, and every copy has to equal the other tree's).  Two things are normalised, both link layout and not code: the s_nop
 padding after a function's last instruction, and the 32-bit literals of the s_add_u32 / s_addc_u32 pair after an s_getpc_b64 (the
-distance to a callee or a constant).  Exit code 1 if a name is missing on either side or a function differs; --diff prints how."""
+distance to a callee or a constant).  A function whose mangled name changed for a reason that is not code (a parameter's type moved to
+another namespace) is paired by hand: --rename OLD=NEW, OLD being the other tree's name (or --rename-file: such a pair a line); it is
+then compared like the rest and listed as renamed.  Names are never paired by guessing: one that is missing on either side without a
+rename fails.  Exit code 1 if a name is missing on either side or a function differs; --diff prints how."""
 import difflib, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
@@ -60,8 +64,43 @@ def functions(objdir):
     return out
 
 
-def compare(other, show):
+def read_renames(args):
+    """{old mangled name: new} from --rename OLD=NEW (repeatable) and --rename-file FILE (a pair a line; blank lines and # comments skipped)"""
+    pairs = []
+    for i, a in enumerate(args):
+        if a == "--rename":
+            pairs.append(args[i + 1])
+        elif a == "--rename-file":
+            with open(args[i + 1]) as f:
+                pairs += [ln.strip() for ln in f if ln.strip() and not ln.lstrip().startswith("#")]
+    renames = {}
+    for p in pairs:
+        old, eq, new = p.partition("=")
+        if not eq or not old or not new or old in renames:
+            sys.exit("--rename wants OLD=NEW, every OLD once: %r" % p)
+        renames[old] = new
+    return renames
+
+
+def renamed(theirs, renames):
+    """the other tree's functions under this tree's names: a renamed function's key, and its name inside its own branch targets"""
+    out = {}
+    for name, copies in theirs.items():
+        new = renames.get(name, name)
+        if new in out or (new != name and new in theirs):
+            sys.exit("--rename: %s exists there already" % new)
+        out[new] = [(obj, [t.replace("<" + name + "+", "<" + new + "+") for t in ins]) for obj, ins in copies] if new != name else copies
+    return out
+
+
+def compare(other, show, renames):
     mine, theirs = functions(BUILD), functions(other)
+    unused = sorted(set(renames) - set(theirs))
+    if unused:
+        sys.exit("--rename: no such function there: " + ", ".join(unused))
+    theirs = renamed(theirs, renames)
+    for old, new in sorted(renames.items()):
+        print("RENAMED  %s  ->  %s" % (old, new))
     gone, new = sorted(set(theirs) - set(mine)), sorted(set(mine) - set(theirs))
     same = differ = 0
     for name in sorted(set(mine) & set(theirs)):
@@ -82,14 +121,14 @@ def compare(other, show):
         for obj, _ in v:
             per[obj] = per.get(obj, 0) + 1
     print("functions per object here: " + ", ".join("%s %d" % (o[:-len(".hip.o")], c) for o, c in sorted(per.items())))
-    print("%d names there, %d here; %d missing here, %d only here; %d copies identical, %d differ"
-          % (len(theirs), len(mine), len(gone), len(new), same, differ))
+    print("%d names there, %d here (%d renamed); %d missing here, %d only here; %d copies identical, %d differ"
+          % (len(theirs), len(mine), len(renames), len(gone), len(new), same, differ))
     return 1 if gone or new or differ else 0
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], "--diff" in sys.argv[3:]))
+        sys.exit(compare(sys.argv[2], "--diff" in sys.argv[3:], read_renames(sys.argv[3:])))
     for name, lines in disassemble(os.path.join(BUILD, sys.argv[1] + ".hip.o")).items():
         if sys.argv[2] in name:
             print("<%s>:\n%s" % (name, "\n".join(lines)))
