@@ -16,6 +16,8 @@
 // that computed them).  A P-refinement appends a segment, so nothing is copied
 // when the degree rises; ReallocCoeffs (:474-555) becomes one gather at the end.
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -97,6 +99,17 @@ struct hpsdf_build {
 namespace hpsdf {
 
 uint64_t jobCost(int degree, int depth, bool coarse);
+
+// Octree.cpp:1078-1086: the nearness weight a fit's error is multiplied by, from |mean FApprox| (:1224-1226 / :1246), with the HOST's
+// pow / exp -- both schedulers call this one (tests/hiprec_weight.py: the values decide refinement, and so the block's bytes)
+inline double nearnessWeight(const hpsdf_config& cfg, double mean) {
+    const double d = std::sqrt(3.0), strength = cfg.weighting_strength;
+    if (cfg.weighting_type == 1) {
+        const double k = std::pow(1.0 - mean / d, strength);
+        return std::min<double>(1.0, std::max<double>(k, 0.0));
+    }
+    return std::exp(-1.0 * strength * mean / d);
+}
 
 // what both schedulers ask of a configuration before they build, and the copy of it that goes into the block
 int validateBuildConfig(const hpsdf_config* cfg);

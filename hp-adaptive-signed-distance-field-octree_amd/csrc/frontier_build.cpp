@@ -452,18 +452,10 @@ int FrontierBuild::applyWeights(const FitBlock* blocks, uint32_t maxBlocks, size
     const double tw = frNow();
     tSync += tw - ts;
     const uint32_t nJobs = world == 1 ? std::min<uint32_t>(ws->hostFlag[0], kFrJobs) : std::min<uint32_t>(nMine, kFrJobs);
-    const double dd = std::sqrt(3.0), strength = cfg.weighting_strength;
     const double* mean = ws->hostMeans + base;
     double* w = ws->hostWeights + base;
     const uint32_t step = round0 ? 9u : 1u;  // round 0: every job is a coarse cell with one fit (slot 0 of its nine)
-    for (uint32_t i = 0; i < nJobs * 9u; i += step) {
-        if (cfg.weighting_type == 1) {
-            const double k = std::pow(1.0 - mean[i] / dd, strength);
-            w[i] = std::min<double>(1.0, std::max<double>(k, 0.0));
-        } else {
-            w[i] = std::exp(-1.0 * strength * mean[i] / dd);
-        }
-    }
+    for (uint32_t i = 0; i < nJobs * 9u; i += step) w[i] = nearnessWeight(cfg, mean[i]);
     std::atomic_thread_fence(std::memory_order_release);
     tWeights += frNow() - tw;
     FR_LAUNCH(fr_weigh_kernel, frLaunchWeigh, s, d, round0 ? 1u : 9u, base, nJobs);

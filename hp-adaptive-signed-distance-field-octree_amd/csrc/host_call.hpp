@@ -1,4 +1,4 @@
-// The *_host entry points of capi.cpp (host arrays in, host arrays out): the context's cached device and pinned scratch, the list an
+// The *_host entry points of capi_field.cpp and capi_tree.cpp (host arrays in, host arrays out): the context's cached device and pinned scratch, the list an
 // entry names its arrays in, and the call that moves them by one of three paths.
 #pragma once
 #include <cstdlib>
@@ -104,6 +104,39 @@ int hostCall(hpsdf_ctx* ctx, HostArrays& list, Run&& run) {
     for (const HostArrays::Slot& s : list)
         if (s.dst && staged) std::memcpy(s.dst, ctx->hostPin + s.off, s.bytes);
     return HPSDF_OK;
+}
+
+// The host call of n points in and one value a point out: run(const double* dXyz, double* dOut) launches on the context stream.
+template <typename Run>
+int hostRoundTrip(hpsdf_ctx* ctx, const double* xyz, size_t n, double* out, Run&& run) {
+    if (n == 0) return HPSDF_OK;
+    HostArrays arr;
+    const auto dXyz = arr.in(xyz, n * 3);
+    const auto dOut = arr.out(out, n);
+    return hostCall(ctx, arr, [&] { return run(dXyz, dOut); });
+}
+
+// Up to how many points / rays a *_host call is answered on the calling thread.  The defaults are where the two paths cost the same on an
+// MI355X box (tools/host_api_latency.py, profiles/r04_host_call_thresholds.txt): a launch round trip is ~15 us (~55 us for the mesh
+// traversal), a point on the host 0.045 us (Query), 0.07 us (gradient), <= 9 us (a ray: up to 200 Query steps), ~23 us (mesh distance).
+// HPSDF_HOST_QUERY_POINTS / _GRADIENT_POINTS / _RAYS / _MESH_POINTS override them (read once).
+inline size_t hostLimit(const char* env, size_t dflt) {
+    const char* e = std::getenv(env);
+    if (!e) return dflt;
+    const long v = std::atol(e);
+    return v < 0 ? 0 : (size_t)v;
+}
+inline size_t hostQueryLimit() { static const size_t v = hostLimit("HPSDF_HOST_QUERY_POINTS", kHostQueryPoints); return v; }
+inline size_t hostGradientLimit() { static const size_t v = hostLimit("HPSDF_HOST_GRADIENT_POINTS", kHostGradientPoints); return v; }
+inline size_t hostRayLimit() { static const size_t v = hostLimit("HPSDF_HOST_RAYS", kHostRays); return v; }
+inline size_t hostMeshLimit() { static const size_t v = hostLimit("HPSDF_HOST_MESH_POINTS", kHostMeshPoints); return v; }
+// HPSDF_SMALL_QUERIES_ON_DEVICE=1 (read once) sends calls of a few points through query_few_kernel as before round 4: a measurement knob
+inline bool smallQueriesOnHost() {
+    static const bool on = [] {
+        const char* e = std::getenv("HPSDF_SMALL_QUERIES_ON_DEVICE");
+        return !(e && e[0] == '1');
+    }();
+    return on;
 }
 
 }  // namespace hpsdf

@@ -248,7 +248,7 @@ inline T* rowOf(T* p, size_t i, size_t stride = 1) {
 
 }  // namespace
 
-// The rows of a call answered on the calling thread: what the *_host entries (capi.cpp, up to kHostQueryPoints / kHostRays rows) and the
+// The rows of a call answered on the calling thread: what the *_host entries (capi_tree.cpp, up to kHostQueryPoints / kHostRays rows) and the
 // *_block entries below run.  The optional outputs are passed as they came in.  The per-row routines with a single caller are kept out of line
 // ([[gnu::noinline]]): compiled into its row loop hostCastRay spilt more of its walk's state, and a one-ray call is what the C++ drop-in's
 // scalar CastRay costs (the instruction counts and the timings: profiles/point_call_plumbing_timing.txt, part B).

@@ -290,7 +290,7 @@ hipError_t launchMeshTriPos(hipStream_t stream, const float* dVerts, const uint3
     return hipGetLastError();
 }
 
-// Mesh::SignedDistanceAtPt(pt, bvh) for a few points, on the calling thread: `hm` holds HOST copies of the field's arrays (capi.cpp
+// Mesh::SignedDistanceAtPt(pt, bvh) for a few points, on the calling thread: `hm` holds HOST copies of the field's arrays (capi_field.cpp
 // keeps them with the field after the first such call).  The per-point stack traversal of meshSignedDistance, compiled for the host
 // from the very statements the device runs: the same bits as every device path (tests/test_gpu_parity.py).
 void meshEvalHostPoints(const MeshDev& hm, const double* xyz, size_t n, double* out) {

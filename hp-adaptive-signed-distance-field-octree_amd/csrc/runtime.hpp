@@ -41,6 +41,20 @@ struct Staged {
     }
 };
 
+// frees its device buffers on every exit path
+struct DevBufs {
+    std::vector<void*> p;
+    ~DevBufs() {
+        for (void* q : p)
+            if (q) (void)hipFree(q);
+    }
+    hipError_t alloc(void** out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+
 // Per-context scratch of the build: the coefficient arena and the per-round staging buffers.  Kept
 // across Create() calls (hipMalloc/hipFree cost more than a whole coarse round).
 struct Workspace {
@@ -231,7 +245,7 @@ int hipFail(hipError_t e, const char* what);
     }
 
 // Query / QueryWithGradient of one point on the calling thread (host_query.cpp): the kernels' values bit for bit
-constexpr size_t kHostQueryPoints = 32;     // Query calls of up to this many points never reach the device (capi.cpp: hostQueryLimit)
+constexpr size_t kHostQueryPoints = 32;     // Query calls of up to this many points never reach the device (host_call.hpp: hostQueryLimit)
 constexpr size_t kHostGradientPoints = 32;  // QueryWithGradient
 constexpr size_t kHostRays = 32;            // QueryRay
 constexpr size_t kHostMeshPoints = 2;       // mesh signed distance (hpsdf_field_eval_host on a plain mesh field): ~23-50 us a point on the host, a launch

@@ -244,7 +244,7 @@ def field_eval(spec, X, Y, Z, left=False):
 
 # ---------------------------------------------------------------------------------------------------------------- fits
 def lattice_cells(depth, n):
-    """The first n cells of the depth-`depth` lattice, x fastest, wrapping after side^3 (hpsdf_fit_cells, capi.cpp) -> f32 bmin, bmax."""
+    """The first n cells of the depth-`depth` lattice, x fastest, wrapping after side^3 (hpsdf_fit_cells, bench_fit.cpp) -> f32 bmin, bmax."""
     side = 1 << depth
     h = np.float32(1.0) / np.float32(side)
     i = np.arange(n) % (side ** 3)

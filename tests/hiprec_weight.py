@@ -46,7 +46,7 @@ No number below was chosen by looking at a kernel's or the oracle's output.
        d(k) = s (|base| + d(base))^(s - 1) d(base) + P u' |k|      for s >= 1 (the derivative is monotone in |base|)
    with P = 1 the error of glibc's pow in ulp and u' = 2u the relative size of an ulp at most.  P = 1 (and E = 1 for exp) are the
    figures of the glibc manual's table "Known Maximum Errors in Math Functions" for x86_64 double; the host forms every weight
-   with glibc (csrc/capi.cpp, the device frontier's host step), the oracle likewise.  max and min are 1-Lipschitz: d(w) = d(k).
+   with glibc (csrc/builder.hpp nearnessWeight, for both schedulers), the oracle likewise.  max and min are 1-Lipschitz: d(w) = d(k).
    The reference's own edge semantics, reproduced:
        m > sqrt 3 makes base < 0.  An odd integer strength (3, the reference's) gives k < 0 and w = 0 exactly; an even integer
        gives k = |base|^s clamped at 1.  A fractional strength gives pow = NaN; std::max<f64>(NaN, 0.0) returns its first

@@ -33,7 +33,7 @@ hipError_t launchFitWeight(hipStream_t, const FitBlock*, uint32_t, size_t, const
 hipError_t launchFitMfma(hipStream_t, int, const FitBlock*, uint32_t, const FitTask*, double*, double*, const DeviceTables*, const FieldDev&,
                          const RootMap&, const uint32_t*) { return hipErrorNoDevice; }
 bool fitSplitSupports(int, int) { return false; }
-static int gLeft = 0;  // capi.cpp's hpsdf_set_reduction_order(); here from HPSDF_REDUCTION_ORDER (main)
+static int gLeft = 0;  // runtime.cpp's hpsdf_set_reduction_order(); here from HPSDF_REDUCTION_ORDER (main)
 int reductionLeftAssoc(const hpsdf_ctx*) { return gLeft; }
 int meshFaceRuleReference(const hpsdf_ctx*) { return 0; }
 void setReductionLeftAssoc(int left) { gLeft = left != 0; }

@@ -261,7 +261,7 @@ def test_scalar_calls_answered_on_the_host_equal_the_kernels(H, O, ctx, golden):
 def test_mesh_scalar_calls_answered_on_the_host_equal_the_kernels(H, O, ctx, monkeypatch, host_build):
     """Mesh::SignedDistanceAtPt(pt, bvh) (Mesh.cpp:54-63) one point at a time -- what a user's SDF lambda written against the
     reference does per sample: calls of one or two points on a plain mesh field are answered on the calling thread from host copies
-    of the field's arrays (capi.cpp meshHostMirror, mesh_field.hip meshEvalHostPoints: the per-point traversal compiled for the
+    of the field's arrays (capi_field.cpp meshHostMirror, mesh_field.hip meshEvalHostPoints: the per-point traversal compiled for the
     host from the statements the device runs).  Same bits as the batched device paths and the O(n) scan -- on a smooth mesh, on
     the reference's own mesh, on a needle mesh, for points on vertices / edges / faces, in the medial region, far away, NaN."""
     from helpers import fuzz_mesh_case, hard_points

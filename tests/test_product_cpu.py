@@ -249,3 +249,14 @@ def test_hook_library_recompiles_exactly_the_units_that_hold_a_hook(H):
     units = [f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp"))]  # (headers are compiled with the units that include them)
     hooked = {s for s in units if "#ifdef HPSDF_TEST_HOOKS" in open(os.path.join(build.CSRC, s), errors="replace").read()}
     assert hooked == set(build.HOOK_SOURCES) and len(build.HOOK_SOURCES) == len(hooked)
+
+
+def test_every_compiled_unit_is_listed_in_the_build(H):
+    """build.SOURCES names every .hip and .cpp file of csrc/ exactly once.  A shared library links with undefined symbols, so a unit that
+    is missing from the list would surface only when somebody calls into it (test_library_exports_every_declared_symbol sees a missing
+    export, not a missing internal function)."""
+    import importlib
+    build = importlib.import_module("hpsdf_amd.build")
+    units = {f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp"))}
+    assert units == set(build.SOURCES), "in csrc/ only: %s; listed only: %s" % (sorted(units - set(build.SOURCES)), sorted(set(build.SOURCES) - units))
+    assert len(build.SOURCES) == len(set(build.SOURCES)), "listed twice: %s" % sorted(s for s in set(build.SOURCES) if build.SOURCES.count(s) > 1)
