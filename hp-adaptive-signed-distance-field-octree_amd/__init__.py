@@ -208,6 +208,13 @@ _SIGNATURES = {
     "hpsdf_extract_surface_sparse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                                C.c_double, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_uint64),
                                                C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.c_void_p]),
+    "hpsdf_extract_surface_dual": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                             C.c_double, C.c_double, C.c_uint32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint8)), C.c_void_p]),
+    "hpsdf_extract_surface_dual_block": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                                   C.c_double, C.c_double, C.c_uint32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint8)), C.c_void_p]),
+    "hpsdf_surface_dual_last_timings": (C.c_int, [C.POINTER(C.c_double)]),
     "hpsdf_surface_classify_host": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                               C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
     "hpsdf_surface_classify_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
@@ -840,6 +847,13 @@ class DeviceTree:
             return verts, tris
         return verts, tris, {k: getattr(st, k) for k, _ in SurfaceSparseStats._fields_ if k != "reserved"}
 
+    def extract_surface_dual(self, lo, hi, n, iso=0.0, tau=0.1, values=False, info=False):
+        """Dual contouring over extract_surface's lattice (include/hpsdf.h, hpsdf_extract_surface_dual): one vertex a mixed cube, placed
+        by the field's tangent planes at the crossing edges (tau: the relative eigenvalue cut of the fit), two triangles an interior
+        crossing edge -> (verts f64 [V,3], tris u64 [T,3]), then the info bytes u8 [V] (rank in bits 0-1, DUAL_CLAMPED) when info is
+        true, then the lattice values f64 [n2+1, n1+1, n0+1] when values is true."""
+        return _dual_call(lambda *a: lib().hpsdf_extract_surface_dual(self.ctx.handle, self.handle, *a), lo, hi, n, iso, tau, values, info)
+
     def classify_surface_blocks(self, lo, hi, n, iso=0.0, first_block=0, count=None):
         """The classification kernel's class byte per block (0 evaluate, 1 all >= iso, 2 all < iso) for blocks [first_block,
         first_block + count), default all of them, x fastest -> u8 [count]."""
@@ -1279,7 +1293,7 @@ class Octree:
         return rgb
 
     def ExtractSurface(self, view_min, view_max, n, iso=0.0, sparse=False, normals=False, project=False, tol=1e-9, max_iter=16,
-                       curvature=False):
+                       curvature=False, dual=False, tau=0.1):
         """Triangle mesh of the level set {Query = iso} over the box [view_min, view_max] with n cubes per axis (an int or three)
         -> (verts f64 [V,3], tris u64 [T,3]); DeviceTree.extract_surface states the lattice.  sparse: the same arrays through
         DeviceTree.extract_surface_sparse (lattices up to 2^40 points).  project: the vertices -- linear interpolants along lattice
@@ -1287,16 +1301,22 @@ class Octree:
         its projection converged within half a cube of it); tris is unchanged.  normals: (verts, tris, normals f64 [V,3]) with
         normals = query_gradient(verts, unit=True)[1], the field's unit gradient at every vertex (the projected ones under project).
         curvature: a last array f64 [V,2] is appended, query_curvature(verts): the level set's (mean, gauss) at the final vertices;
-        verts and tris are the same bytes with and without it."""
+        verts and tris are the same bytes with and without it.  dual: dual contouring instead of marching cubes
+        (DeviceTree.extract_surface_dual with tau): one vertex a cube, creases and corners kept; normals and curvature apply to its
+        vertices as to any; with sparse or project it raises ValueError."""
         if self._tree is None:
             raise HpsdfError(6, "Query on an empty octree")
+        if dual and (sparse or project):
+            raise ValueError("dual=True does not combine with sparse or project")
         n3 = (int(n),) * 3 if np.ndim(n) == 0 else tuple(int(x) for x in n)
         if curvature:
-            res = self.ExtractSurface(view_min, view_max, n3, iso, sparse, normals, project, tol, max_iter)
+            res = self.ExtractSurface(view_min, view_max, n3, iso, sparse, normals, project, tol, max_iter, False, dual, tau)
             return res + (self._tree.query_curvature(res[0]),)
         if normals:
-            verts, tris = self.ExtractSurface(view_min, view_max, n3, iso, sparse, False, project, tol, max_iter)
+            verts, tris = self.ExtractSurface(view_min, view_max, n3, iso, sparse, False, project, tol, max_iter, False, dual, tau)
             return verts, tris, self._tree.query_gradient(verts, unit=True)[1]
+        if dual:
+            return self._tree.extract_surface_dual(view_min, view_max, n3, iso, tau)
         if sparse:
             verts, tris = self._tree.extract_surface_sparse(view_min, view_max, n3, iso)
         else:
@@ -1345,6 +1365,8 @@ class SurfaceSparseStats(C.Structure):  # hpsdf_surface_sparse_stats, 96 bytes
 
 
 SURFACE_BLOCK = 8  # HPSDF_SURFACE_BLOCK
+DUAL_SWEEPS = 5  # HPSDF_DUAL_SWEEPS
+DUAL_CLAMPED = 4  # HPSDF_DUAL_CLAMPED
 GRADIENT_UNIT = 1  # HPSDF_GRADIENT_UNIT
 PROJECT_UNIT = 1  # HPSDF_PROJECT_UNIT
 PROJECT_CONVERGED, PROJECT_ITER_LIMIT, PROJECT_LEFT_ROOT, PROJECT_FLAT = 0, 1, 2, 3  # HPSDF_PROJECT_*: out_status
@@ -1550,6 +1572,42 @@ def _take_mesh(call):
     lib()._libc.free(C.cast(v, C.c_void_p))
     lib()._libc.free(C.cast(t, C.c_void_p))
     return verts, tris
+
+
+def _dual_call(call, lo, hi, n, iso, tau, values, info):
+    """call(lo, hi, n, iso, tau, flags, verts, n_verts, tris, n_tris, vert_info, values): a dual extraction's malloc'd result as arrays,
+    the C arrays freed.  The vertices come back whenever there are any, with or without triangles."""
+    lo3, hi3, n3 = _lattice_args(lo, hi, n)
+    vals = np.empty((int(n[2]) + 1, int(n[1]) + 1, int(n[0]) + 1)) if values else None
+    v, t, b = C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
+    nv, nt = C.c_uint64(), C.c_uint64()
+    check(call(lo3, hi3, n3, float(iso), float(tau), 0, C.byref(v), C.byref(nv), C.byref(t), C.byref(nt), C.byref(b) if info else None,
+               vals.ctypes.data_as(C.c_void_p) if values else None))
+    verts, tris, inf = np.zeros((0, 3)), np.zeros((0, 3), np.uint64), np.zeros(0, np.uint8)
+    if nv.value:
+        verts = np.ctypeslib.as_array(v, shape=(nv.value, 3)).copy()
+        if info:
+            inf = np.ctypeslib.as_array(b, shape=(nv.value,)).copy()
+    if nt.value:
+        tris = np.ctypeslib.as_array(t, shape=(nt.value, 3)).copy()
+    for p in (v, t, b):
+        lib()._libc.free(C.cast(p, C.c_void_p))
+    return (verts, tris) + ((inf,) if info else ()) + ((vals,) if values else ())
+
+
+def extract_surface_dual_block(block, lo, hi, n, iso=0.0, tau=0.1, values=False, info=False):
+    """hpsdf_extract_surface_dual_block: DeviceTree.extract_surface_dual's arrays from a serialised block on the calling thread (no
+    device; the process-wide reduction order)."""
+    buf = bytes(block)
+    return _dual_call(lambda *a: lib().hpsdf_extract_surface_dual_block(buf, len(buf), *a), lo, hi, n, iso, tau, values, info)
+
+
+def surface_dual_last_timings():
+    """Device milliseconds of the phases of this thread's last extract_surface_dual: lattice, ballots, scan, hermite, vertices, quads,
+    d2h, total."""
+    out = (C.c_double * 8)()
+    check(lib().hpsdf_surface_dual_last_timings(out))
+    return dict(zip(("lattice", "ballots", "scan", "hermite", "vertices", "quads", "d2h", "total"), list(out)))
 
 
 def surface_block_count(n):

@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -18,7 +19,10 @@
 #include <vector>
 
 #include "block.hpp"
+#include "dual_vertex.hpp"
+#include "edge_vertex.hpp"
 #include "integrate.hpp"
+#include "lattice_check.hpp"
 #include "leaf_gradient.hpp"
 #include "leaf_hessian.hpp"
 #include "ray_cast.hpp"
@@ -503,9 +507,161 @@ int treeFromBlock(const void* block, size_t size, hpsdf_tree& t, int& leftAssoc)
     return HPSDF_OK;
 }
 
+// ExtractSurfaceDual (include/hpsdf.h) on the calling thread: the phases of surface_dual.hip as loops -- the lattice values through
+// hostQueryPoint, the three bit words and their prefixes, a record a crossing edge through edgeVertex and hostQueryPointTrueGradient,
+// a vertex a mixed cube through dual_vertex.hpp, two triangles an interior crossing edge.  The outputs are malloc'd last: nothing is
+// allocated on an error.
+struct BitWords {
+    std::vector<uint64_t> words, prefix;  // prefix[w]: set bits in the words before w; prefix.back(): all of them
+    explicit BitWords(uint64_t bits) : words((bits + 63) / 64, 0), prefix((bits + 63) / 64 + 1, 0) {}
+    void set(uint64_t i) { words[i >> 6] |= 1ull << (i & 63u); }
+    bool test(uint64_t i) const { return (words[i >> 6] >> (i & 63u)) & 1u; }
+    void scan() {
+        for (size_t w = 0; w < words.size(); ++w) prefix[w + 1] = prefix[w] + (uint64_t)__builtin_popcountll(words[w]);
+    }
+    uint64_t rank(uint64_t i) const { return prefix[i >> 6] + (uint64_t)__builtin_popcountll(words[i >> 6] & ((1ull << (i & 63u)) - 1ull)); }
+    uint64_t count() const { return prefix.back(); }
+};
+
+int hostExtractSurfaceDual(const hpsdf_tree& t, const CheckedLattice& cl, double iso, double tau, int leftAssoc, double** verts, uint64_t* nVerts,
+                           uint64_t** tris, uint64_t* nTris, uint8_t** vertInfo, double* values) {
+    const uint32_t n[3] = {cl.n[0], cl.n[1], cl.n[2]}, np[3] = {cl.n[0] + 1u, cl.n[1] + 1u, cl.n[2] + 1u};
+    const uint32_t stride[3] = {1u, np[0], np[0] * np[1]};
+    const uint64_t nPts = cl.nPts, nEdges = 3 * nPts, nCubes = cl.nCubes;
+    std::vector<double> v(nPts);
+    for (uint64_t L = 0; L < nPts; ++L) {
+        const uint32_t i = (uint32_t)(L % np[0]), r = (uint32_t)(L / np[0]), j = r % np[1], k = r / np[1];
+        const double x[3] = {cl.lo[0] + (double)i * cl.h[0], cl.lo[1] + (double)j * cl.h[1], cl.lo[2] + (double)k * cl.h[2]};
+        v[L] = hostQueryPoint(t, x);
+    }
+    const auto edgeOf = [&](uint64_t e, uint32_t& L, uint32_t& a, uint32_t (&idx)[3]) {
+        L = (uint32_t)(e / 3u), a = (uint32_t)(e - 3u * (uint64_t)L);
+        idx[0] = L % np[0], idx[1] = (L / np[0]) % np[1], idx[2] = (L / np[0]) / np[1];
+    };
+    BitWords crossing(nEdges), interior(nEdges), mixed(nCubes);
+    for (uint64_t e = 0; e < nEdges; ++e) {
+        uint32_t L, a, idx[3];
+        edgeOf(e, L, a, idx);
+        if (idx[a] >= n[a] || (v[L] < iso) == (v[L + stride[a]] < iso)) continue;
+        crossing.set(e);
+        if (dualInterior(idx, a, n)) interior.set(e);
+    }
+    const uint32_t cornerOff[8] = {0u, 1u, stride[1], stride[1] + 1u, stride[2], stride[2] + 1u, stride[2] + stride[1], stride[2] + stride[1] + 1u};
+    const auto cubeBase = [&](uint64_t Q, uint32_t (&idx)[3]) {
+        idx[0] = (uint32_t)(Q % n[0]), idx[1] = (uint32_t)((Q / n[0]) % n[1]), idx[2] = (uint32_t)((Q / n[0]) / n[1]);
+        return idx[0] + np[0] * (idx[1] + np[1] * idx[2]);
+    };
+    for (uint64_t Q = 0; Q < nCubes; ++Q) {
+        uint32_t idx[3], c = 0;
+        const uint32_t L0 = cubeBase(Q, idx);
+        for (int b = 0; b < 8; ++b) c |= (v[L0 + cornerOff[b]] < iso ? 1u : 0u) << b;
+        if (c != 0u && c != 255u) mixed.set(Q);
+    }
+    crossing.scan(), interior.scan(), mixed.scan();
+    const uint64_t E = crossing.count(), V = mixed.count(), T = 2 * interior.count();
+
+    std::vector<DualRecord> recs(E);
+    for (uint64_t e = 0; e < nEdges; ++e) {
+        if (!crossing.test(e)) continue;
+        uint32_t L, a, idx[3];
+        edgeOf(e, L, a, idx);
+        DualRecord& r = recs[crossing.rank(e)];
+        edgeVertex(cl.lo, cl.h, idx, a, v[L], v[L + stride[a]], iso, r.p);
+        hostQueryPointTrueGradient(t, r.p, false, leftAssoc, &r.f, r.g);
+        r.pad = 0.0;
+    }
+    struct Malloced {  // released unless handed to the caller
+        void* p = nullptr;
+        ~Malloced() { std::free(p); }
+    } hVerts, hTris, hInfo;
+    if (V > 0) {
+        hVerts.p = std::malloc(V * 3 * sizeof(double));
+        if (T > 0) hTris.p = std::malloc(T * 3 * sizeof(uint64_t));
+        if (vertInfo) hInfo.p = std::malloc(V);
+        if (!hVerts.p || (T > 0 && !hTris.p) || (vertInfo && !hInfo.p))
+            return fail(HPSDF_ERR_OUT_OF_MEMORY, "hpsdf_extract_surface_dual_block: host allocation failed");
+    }
+    double* outV = (double*)hVerts.p;
+    uint64_t* outT = (uint64_t*)hTris.p;
+    uint8_t* outI = (uint8_t*)hInfo.p;
+    for (uint64_t Q = 0, vtx = 0; Q < nCubes; ++Q) {
+        if (!mixed.test(Q)) continue;
+        uint32_t idx[3], k = 0;
+        const uint32_t L0 = cubeBase(Q, idx);
+        const DualRecord* rec[12];
+        DualNormal N;
+        double sum[3], m[3];
+        dualClear(N, sum);
+        for (uint32_t e = 0; e < 12u; ++e) {
+            const uint64_t ge = 3u * (uint64_t)(L0 + cornerOff[dualEdgeCorner(e)]) + dualEdgeAxis(e);
+            if (!crossing.test(ge)) continue;
+            rec[k] = &recs[crossing.rank(ge)];
+            dualAddPoint(rec[k]->p, sum);
+            ++k;
+        }
+        dualMean(sum, k, m);
+        for (uint32_t c = 0; c < k; ++c) dualAccumulate(rec[c]->p, rec[c]->f, rec[c]->g, m, iso, leftAssoc, N);
+        double cubeLo[3], cubeHi[3], x[3];
+        for (int a = 0; a < 3; ++a) {
+            cubeLo[a] = cl.lo[a] + (double)idx[a] * cl.h[a];
+            cubeHi[a] = cl.lo[a] + (double)(idx[a] + 1u) * cl.h[a];
+        }
+        const uint32_t info = dualSolve(N, m, tau, leftAssoc, cubeLo, cubeHi, x);
+        outV[3 * vtx] = x[0], outV[3 * vtx + 1] = x[1], outV[3 * vtx + 2] = x[2];
+        if (outI) outI[vtx] = (uint8_t)info;
+        ++vtx;
+    }
+    for (uint64_t e = 0; e < nEdges && T > 0; ++e) {
+        if (!interior.test(e)) continue;
+        uint32_t L, a, idx[3], Q[4];
+        edgeOf(e, L, a, idx);
+        dualQuadCubes(idx, a, n, Q);
+        uint64_t q[4];
+        for (int c = 0; c < 4; ++c) q[c] = mixed.rank(Q[c]);
+        if (!(v[L] < iso)) std::swap(q[1], q[3]);  // the lower end is outside: the quad is reversed
+        uint64_t* o = outT + 6 * interior.rank(e);
+        o[0] = q[0], o[1] = q[1], o[2] = q[2];
+        o[3] = q[0], o[4] = q[2], o[5] = q[3];
+    }
+    if (values) std::memcpy(values, v.data(), nPts * sizeof(double));
+    if (V > 0) {
+        *verts = outV, *tris = outT, *nVerts = V, *nTris = T;
+        if (vertInfo) *vertInfo = outI;
+        hVerts.p = hTris.p = hInfo.p = nullptr;
+    }
+    return HPSDF_OK;
+}
+
 }  // namespace
 
+// what hpsdf_extract_surface_dual[_block] reject before anything runs, besides the lattice (0: fine)
+int dualArgumentError(double tau, uint32_t flags) {
+    if (flags != 0u) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_extract_surface_dual: flags must be 0");
+    if (!(tau >= 0.0 && tau < 1.0)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_extract_surface_dual: tau must be finite with 0 <= tau < 1");
+    return HPSDF_OK;
+}
+
 }  // namespace hpsdf
+
+// ExtractSurfaceDual from a serialised block, on the calling thread (no device; the process-wide reduction order)
+extern "C" int hpsdf_extract_surface_dual_block(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3],
+                                                double iso, double tau, uint32_t flags, double** verts, uint64_t* n_verts, uint64_t** tris,
+                                                uint64_t* n_tris, uint8_t** vert_info, double* values) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (!lo || !hi || !n || !verts || !n_verts || !tris || !n_tris) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
+    if (vert_info) *vert_info = nullptr;
+    if (const int rc = dualArgumentError(tau, flags)) return rc;
+    hpsdf_tree t;
+    int left;
+    if (const int rc = treeFromBlock(block, size, t, left)) return rc;
+    CheckedLattice cl{};
+    if (const int rc = checkLattice("hpsdf_extract_surface_dual_block", kDenseLimits, t.dev.rootCentre, t.dev.rootInvSizes, lo, hi, n, iso, &cl))
+        return rc;
+    return hostExtractSurfaceDual(t, cl, iso, tau, left, verts, n_verts, tris, n_tris, vert_info, values);
+    HPSDF_CATCH
+}
 
 // QueryGradient from a serialised block, on the calling thread: no device, no context; treeFromBlock makes the tree the rows are
 // answered from.

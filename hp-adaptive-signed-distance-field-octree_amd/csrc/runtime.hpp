@@ -269,6 +269,7 @@ int hessianArgumentError(uint32_t flags, const double* xyz, size_t n, const doub
 int projectArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter);
 int castArgumentError(uint32_t flags, double iso, double tol, uint32_t maxIter, uint32_t maxCells, size_t n, const void* origins, const void* dirs,
                       const void* tMax, const void* outStatus);
+int dualArgumentError(double tau, uint32_t flags);  // hpsdf_extract_surface_dual[_block]; the lattice arguments: lattice_check.hpp
 
 // innermost non-CSG field and the FieldDev the kernels take
 const hpsdf_field* innermost(const hpsdf_field* f);

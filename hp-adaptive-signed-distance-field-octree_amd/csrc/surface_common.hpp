@@ -1,8 +1,9 @@
 // What hpsdf_extract_surface (surface.hip) and hpsdf_extract_surface_sparse (surface_sparse.hip) share.  The sparse call promises the
 // dense call's mesh bit for bit, so everything both must agree on is written here once: the packed case table and its decode, the
-// vertex arithmetic, the wave helpers, the check of the lattice arguments (lattice_check.hpp, included here: QueryBounds' grid entries
+// vertex arithmetic (edge_vertex.hpp, included here), the wave helpers, the check of the lattice arguments (lattice_check.hpp, included here: QueryBounds' grid entries
 // share it) and the host scaffolding of a call (events, the malloc'd outputs; device memory and rocPRIM's two-call pattern are
-// dev_pool.hpp's, which Integrate shares).  Included by those two units only; each gets its own __constant__ copies.
+// dev_pool.hpp's, which Integrate shares).  Included by those two units and by the dual call's (surface_dual.hip: same
+// lattice, same scaffolding) only; each gets its own __constant__ copies.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "dev_pool.hpp"
+#include "edge_vertex.hpp"
 #include "host_call.hpp"
 #include "lattice_check.hpp"
 #include "runtime.hpp"
@@ -64,18 +66,7 @@ __device__ __forceinline__ uint32_t caseEdge(uint64_t pk, uint32_t tr, int m) { 
 __device__ __forceinline__ uint8_t caseCorner(uint64_t pk, uint32_t tr, int m) { return kEdgeCorner[caseEdge(pk, tr, m)]; }
 __device__ __forceinline__ uint8_t caseAxis(uint64_t pk, uint32_t tr, int m) { return kEdgeAxis[caseEdge(pk, tr, m)]; }
 
-// ---- vertex arithmetic (include/hpsdf.h) -------------------------------------------------------------------------------------------
-
-// The vertex on the edge from lattice point idx = (i, j, k) along axis a, whose ends hold va and vb.  Both calls' vertices are these
-// statements in this order; no multiply-add is fused (the build's -ffp-contract=off).
-__host__ __device__ __forceinline__ void edgeVertex(const double* lo, const double* h, const uint32_t (&idx)[3], uint32_t a, double va, double vb,
-                                                    double iso, double (&p)[3]) {
-    const double t = (iso - va) / (vb - va);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) p[d] = lo[d] + (double)idx[d] * h[d];
-    const double xb = lo[a] + (double)(idx[a] + 1u) * h[a];
-    p[a] = p[a] + t * (xb - p[a]);
-}
+// ---- vertex arithmetic (include/hpsdf.h): edgeVertex, edge_vertex.hpp (the dual call's host path shares it) -----------------------
 
 // ---- wave helpers ------------------------------------------------------------------------------------------------------------------
 

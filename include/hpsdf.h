@@ -628,6 +628,69 @@ HPSDF_API int hpsdf_surface_classify_host(const void* block, size_t size, const 
 HPSDF_API int hpsdf_surface_classify_device(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3],
                                             const uint32_t n[3], double iso, uint64_t first_block, uint64_t count, uint8_t* out);
 
+/* ---- ExtractSurfaceDual: dual contouring over the same lattice -- one vertex a cube, placed by the field's tangent planes, so creases
+ * and corners of the solid survive (no reference counterpart) ------------------------------------------------------------------------
+ * Carried over from hpsdf_extract_surface unchanged: the lattice, its limits and checks ((n0+1)(n1+1)(n2+1) <= 2^30, the containment
+ * requirement), the point arithmetic lo + (double)i * h, the lattice values, the classification v < iso, the cube cases, the edge ids
+ * 3 L + axis, the cube order Q = i + n0 (j + n1 k), the cube-local edge numbering 0..11, malloc'd outputs the caller frees, and that
+ * on any error nothing is allocated.  tau must be finite with 0 <= tau < 1 and flags must be 0; anything else is
+ * HPSDF_ERR_INVALID_ARGUMENT.
+ * Hermite sample, one per crossing edge e (an edge whose ends differ in insideness): p_e is hpsdf_extract_surface's vertex of that
+ * edge, by the same statements with the same bits; (f_e, g_e) is QueryGradient (hpsdf_query_true_gradient_*, flags 0: not
+ * normalised) at p_e on the same context, bit for bit.
+ * Vertex: one per mixed cube (case neither 0 nor 255), numbered in increasing Q.  With the cube's k crossing edges taken in
+ * cube-local order 0..11, every statement rounded once, no fused multiply-add, sums started from 0.0:
+ *     s = sum_e p_e (per axis, in that order),  m = s / (double)k,  d_e = p_e - m,
+ *     r_e = (iso - f_e) + sum3(g_e0 d_e0, g_e1 d_e1, g_e2 d_e2)      sum3(a, b, c) = a + (b + c), or (a + b) + c under reduction
+ *                                                                     order 1 (the context's; as in CastRays),
+ *     A_ij = A_ij + g_ei g_ej (all nine, so A stays symmetric),  b_i = b_i + g_ei r_e       in edge order.
+ * A is decomposed by cyclic Jacobi: V = I, then HPSDF_DUAL_SWEEPS sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r the third
+ * index.  A rotation is skipped when A_pq is exactly 0; otherwise
+ *     theta = (A_qq - A_pp) / (2.0 * A_pq),   t = 1.0 / (|theta| + sqrt(theta * theta + 1.0)),  negated if theta < 0,
+ *     c = 1.0 / sqrt(t * t + 1.0),  s = t * c,
+ *     A_pp = A_pp - t * A_pq,  A_qq = A_qq + t * A_pq,  A_pq = A_qp = 0,
+ *     (A_rp, A_rq) = (c * A_rp - s * A_rq,  s * A_rp + c * A_rq)  from the old pair, mirrored into A_pr, A_qr,
+ *     (V_kp, V_kq) = (c * V_kp - s * V_kq,  s * V_kp + c * V_kq)  for k = 0, 1, 2.
+ * The number of sweeps is fixed; there is no data-dependent loop.  lambda_i = A_ii, v_i = column i of V, lambda_max the largest of
+ * the three.  Starting from x = m, for i = 0, 1, 2 with lambda_i > tau * lambda_max and lambda_i > 0:
+ *     w = sum3(V_0i b_0, V_1i b_1, V_2i b_2) / lambda_i,   x_a = x_a + V_ai * w,
+ * the rank being the number of such i.  If lambda_max is not positive or not finite, or a coordinate of x is not finite, x = m and
+ * the rank is 0 (a cube whose samples all lie in leaves of degree 0 has A = 0).  Then x_a is clamped into [X_a(i_a), X_a(i_a + 1)],
+ * the lattice coordinates lo[a] + (double)i * h[a] of the cube's corner points.  vert_info[v]: the rank in bits 0-1,
+ * HPSDF_DUAL_CLAMPED if an axis was clamped.
+ * Sweeps: HPSDF_DUAL_SWEEPS = 5, chosen so that after the last sweep the largest |off-diagonal| entry is at most 2^-40 of the trace.
+ * Measured through the _block entry over every cube of tests/test_surface_dual_cpu.py (87 273 of them; test_jacobi_sweeps_suffice):
+ * 2.6e-101 of the trace after 5 sweeps, 1.1e-24 after 4, 1.2e-6 after 3 -- cyclic Jacobi converges quadratically.
+ * Triangles: a crossing edge along axis a at lattice point (i, j, k) is interior when its indices on the other two axes
+ * b = (a + 1) % 3 and c = (a + 2) % 3 lie in [1, n - 1].  An interior crossing edge gives one quad over the vertices of the four
+ * cubes at (b, c) offsets (-1,-1), (0,-1), (0,0), (-1,0) from (i, j, k) -- q0 q1 q2 q3, counter-clockwise seen from +a -- taken as
+ * q0 q3 q2 q1 when the edge's lower end is outside (v >= iso), and split as (q0, q1, q2), (q0, q2, q3).  Triangles are ordered by
+ * edge id, two per interior crossing edge; normals point towards increasing value, as with marching cubes.  Crossing edges on the
+ * lattice's boundary give nothing: the mesh is open where the surface leaves the box.
+ * Results: the vertices are returned whenever there is a mixed cube, even without a triangle; an empty result is HPSDF_OK with
+ * counts 0 and NULL pointers.  vert_info (may be NULL): *vert_info is a malloc'd byte a vertex (NULL without vertices).  values (may
+ * be NULL): every lattice value, L order.
+ * Limits: one vertex a cube means that a cube face with four crossing edges (an ambiguous face) makes a non-manifold edge between
+ * the two cubes' vertices.  The mesh is always closed where the surface stays inside the lattice (every directed edge has its
+ * reverse, counted with multiplicity); it is edge-manifold where no face is ambiguous.
+ * Device scratch: 8 bytes a lattice point for the values, ~1.6 more for the three bit words (crossing edges, interior crossing
+ * edges, mixed cubes), their counts and prefixes, then 64 bytes a crossing edge (the Hermite record), 4 + 25 a mixed cube (the list,
+ * the vertex and its info byte) and 24 a triangle; all of it is freed before the call returns.
+ * _block: the same statements on the calling thread from a serialised block -- no device, the process-wide reduction order, blocks
+ * accepted and refused as by hpsdf_project_block -- with the same bits in every output as the device call. */
+#define HPSDF_DUAL_SWEEPS 5
+#define HPSDF_DUAL_CLAMPED 4u
+HPSDF_API int hpsdf_extract_surface_dual(hpsdf_ctx* ctx, const hpsdf_tree* t, const double lo[3], const double hi[3], const uint32_t n[3],
+                                         double iso, double tau, uint32_t flags, double** verts, uint64_t* n_verts, uint64_t** tris,
+                                         uint64_t* n_tris, uint8_t** vert_info /* may be NULL */, double* values /* may be NULL */);
+HPSDF_API int hpsdf_extract_surface_dual_block(const void* block, size_t size, const double lo[3], const double hi[3], const uint32_t n[3],
+                                               double iso, double tau, uint32_t flags, double** verts, uint64_t* n_verts, uint64_t** tris,
+                                               uint64_t* n_tris, uint8_t** vert_info /* may be NULL */, double* values /* may be NULL */);
+/* device milliseconds of the phases of this thread's last hpsdf_extract_surface_dual: [0] lattice values, [1] the three ballots and
+ * their counts, [2] scans, [3] Hermite samples, [4] cube list and vertices, [5] quads, [6] download, [7] the whole call from its first
+ * launch (events on the context stream) */
+HPSDF_API int hpsdf_surface_dual_last_timings(double ms[8]);
+
 /* ---- QueryBounds: a guaranteed range of Query over axis-aligned boxes (no reference counterpart) ---------------------------------------
  * One row per box: six doubles, the lower corner a[3] then the upper corner b[3], world coordinates.  The result is an interval
  * [lo, hi] with this guarantee: for every point x with a <= x <= b componentwise, Query(x) -- the double this library computes at x,

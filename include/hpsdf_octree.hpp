@@ -590,6 +590,31 @@ class Octree {
         return m;
     }
 
+    /// Dual contouring over the same lattice: one vertex a cube, placed by the field's tangent planes at the cube's crossing edges, so
+    /// creases and corners of the solid survive (no reference counterpart; include/hpsdf.h, hpsdf_extract_surface_dual).  tau_: the
+    /// relative eigenvalue cut of the fit, 0 <= tau_ < 1.  The vertices come back whenever there are any, with or without triangles
+    SurfaceMesh ExtractSurfaceDual(const Eigen::AlignedBox3f& area_, const Eigen::Vector3i& resolution_, f64 iso_ = 0.0, f64 tau_ = 0.1) const {
+        hpsdf_tree* t = deviceTree();
+        if (!t) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        const double lo[3] = {area_.min()(0), area_.min()(1), area_.min()(2)};
+        const double hi[3] = {area_.max()(0), area_.max()(1), area_.max()(2)};
+        uint32_t n[3];
+        for (int a = 0; a < 3; ++a) {
+            if (resolution_(a) < 1) throw Error(HPSDF_ERR_INVALID_ARGUMENT, "resolution must be at least 1 per axis");
+            n[a] = (uint32_t)resolution_(a);
+        }
+        double* v = nullptr;
+        uint64_t* tr = nullptr;
+        uint64_t nv = 0, nt = 0;
+        check(hpsdf_extract_surface_dual(ctx_, t, lo, hi, n, iso_, tau_, 0u, &v, &nv, &tr, &nt, nullptr, nullptr));
+        SurfaceMesh m;
+        if (nv) m.vertices.assign(v, v + 3 * nv);
+        if (nt) m.triangles.assign(tr, tr + 3 * nt);
+        std::free(v);
+        std::free(tr);
+        return m;
+    }
+
     /// Moves pt_ onto the level set {Query = iso_} by Newton's iteration along the gradient, until |Query - iso_| <= tol_ or maxIter_
     /// steps (no reference counterpart; include/hpsdf.h, "ProjectToSurface").  Returns the status: HPSDF_PROJECT_CONVERGED,
     /// _ITER_LIMIT (near creases the iteration can hop between two cells for ever), _LEFT_ROOT or _FLAT; projected_ is where it stopped.
