@@ -194,6 +194,9 @@ _SIGNATURES = {
     "hpsdf_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_integrate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_integrate_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_simplify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
+    "hpsdf_simplify_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
+    "hpsdf_simplify_transfer": (C.c_int, [C.c_void_p]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p]),
     "hpsdf_query_ray_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -1275,6 +1278,18 @@ class Octree:
             raise HpsdfError(6, "Query on an empty octree")
         return self._tree.integrate(iso, depth, samples, max_cells, cells)
 
+    def Simplify(self, rms, merge=True, truncate=True, stats=False):
+        """A NEW Octree on the same context whose field is within `rms` of this one's in the root-normalised L2 sense, leaf cell by leaf
+        cell (include/hpsdf.h, "Simplify"): sibling leaves merged into their parent, top degrees dropped, from the coefficients alone.
+        This tree is not modified.  stats: (octree, stats dict)."""
+        if self._tree is None:
+            raise HpsdfError(6, "Simplify on an empty octree")
+        block, st = simplify(self.ctx, self.block, rms, merge, truncate)
+        o = Octree(self._device, self._stream, self.K)
+        o._ctx = self._ctx
+        o.FromMemoryBlock(block)
+        return (o, st) if stats else o
+
     def QueryRay(self, origins, directions, t_max):
         """Octree::QueryRay (Octree.h:75) for one ray -> (hit, t) or (n,3) arrays -> (hit[n], t[n])."""
         if self._tree is None:
@@ -1514,6 +1529,52 @@ def integrate_block(block, iso=0.0, depth=8, samples=2, max_cells=1 << 24, cells
     """hpsdf_integrate_block: DeviceTree.integrate's result from a serialised block on the calling thread (no device)."""
     buf = bytes(block)
     return _integrate(lambda *rest: lib().hpsdf_integrate_block(buf, len(buf), *rest), iso, depth, samples, max_cells, cells)
+
+
+SIMPLIFY_MERGE, SIMPLIFY_TRUNCATE = 1, 2  # HPSDF_SIMPLIFY_*
+
+
+class SimplifyStats(C.Structure):  # hpsdf_simplify_stats, 88 bytes
+    _fields_ = [(n, C.c_uint64) for n in ("nodes_in", "coeffs_in", "leaves_in", "nodes_out", "coeffs_out", "leaves_out", "merges",
+                                          "truncations", "levels")] + [("error_bound", C.c_double), ("max_cell_rms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _simplify_flags(merge, truncate):
+    return (SIMPLIFY_MERGE if merge else 0) | (SIMPLIFY_TRUNCATE if truncate else 0)
+
+
+def simplify_block(block, rms, merge=True, truncate=True, flags=None):
+    """hpsdf_simplify_block: a coarser tree within `rms` of the block's, cell by cell (include/hpsdf.h, "Simplify"), on the calling
+    thread with no device -> (block bytes, stats dict).  flags overrides merge / truncate with raw HPSDF_SIMPLIFY_* bits."""
+    buf = bytes(block)
+    blk, sz, st = C.c_void_p(), C.c_size_t(), SimplifyStats()
+    check(lib().hpsdf_simplify_block(buf, len(buf), float(rms), _simplify_flags(merge, truncate) if flags is None else int(flags),
+                                     C.byref(blk), C.byref(sz), C.byref(st)))
+    data = C.string_at(blk, sz.value)
+    lib()._libc.free(blk)
+    return data, st.as_dict()
+
+
+def simplify(ctx, block, rms, merge=True, truncate=True, flags=None):
+    """hpsdf_simplify: simplify_block's bytes and stats, computed on ctx's device."""
+    buf = bytes(block)
+    blk, sz, st = C.c_void_p(), C.c_size_t(), SimplifyStats()
+    rc = lib().hpsdf_simplify(ctx.handle, buf, len(buf), float(rms), _simplify_flags(merge, truncate) if flags is None else int(flags),
+                              C.byref(blk), C.byref(sz), C.byref(st))
+    if rc:
+        ctx._blocks.clear()
+    check(rc)
+    return ctx._take_block(blk, sz.value), st.as_dict()
+
+
+def simplify_transfer():
+    """hpsdf_simplify_transfer: Simplify's transfer matrices -> f64 [2, 13, 13] (lower half, upper half of an axis)."""
+    out = np.zeros((2, 13, 13))
+    check(lib().hpsdf_simplify_transfer(out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def cells_to_boxes(block_or_tree, cells):

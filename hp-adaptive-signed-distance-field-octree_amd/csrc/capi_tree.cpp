@@ -12,6 +12,7 @@
 #include "launch.hpp"
 #include "ray_cast.hpp"
 #include "runtime.hpp"
+#include "simplify.hpp"
 #include "tree_bound.hpp"
 
 using namespace hpsdf;
@@ -495,6 +496,29 @@ int hpsdf_integrate_host(hpsdf_ctx* ctx, const hpsdf_tree* t, double iso, uint32
     if (const int hc = t->boundHostCopies(ctx)) return hc;
     const IntegrateArgs a{iso, depth, samples, maxCells};
     return hostIntegrate(clsTreeOnHost(t), t->hRecs.size(), a, out, outCells, outCount);
+    HPSDF_CATCH
+}
+
+// Simplify (include/hpsdf.h): a coarser tree from a serialised one, within an RMS bound (simplify.hip, simplify.hpp; the device-free
+// entry is simplify_host.cpp's)
+int hpsdf_simplify(hpsdf_ctx* ctx, const void* block, size_t size, double rms, uint32_t flags, void** out_block, size_t* out_size,
+                   hpsdf_simplify_stats* stats) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = simplifyArgumentError(rms, flags, out_block, out_size)) return rc;
+    const Tables& T = tables();
+    BlockView v;
+    BlockMirror m;
+    std::string why;
+    int rc = readBlock(block, size, v, why);
+    if (!rc) rc = mirrorBlock(v, T, m, why);
+    if (rc) return fail(rc, why);
+    HPSDF_HIP(hipSetDevice(ctx->device));
+    SimpState s;
+    simplifyBegin(v, m, T, s);
+    if (const int drc = simplifyOnDevice(ctx, v, m, rms, flags, s)) return drc;
+    rc = simplifyAssemble(v, T, s, [ctx](size_t n) { return ctx->allocBlock(n); }, out_block, out_size, stats, why);
+    return rc ? fail(rc, why) : HPSDF_OK;
     HPSDF_CATCH
 }
 

@@ -17,6 +17,7 @@ struct DeviceTables {
     double rec[13][2];   // Legendre recurrence constants
     uint8_t bidx[456][4];  // basis index (i, j, k) and i+j+k per coefficient row
     uint32_t count[16];    // coefficient count per degree (count[6] == 83)
+    double transfer[2][13][13];  // Simplify's transfer matrices (tables.hpp), lower half then upper half
 };
 
 // 8-byte node record of the query-side tree mirror.  The 56-byte serialised

@@ -222,6 +222,7 @@ int hpsdf_ctx_create(int device, void* stream, hpsdf_ctx** out) {
         h->bidx[i][3] = (uint8_t)(T.basisIndex[i][0] + T.basisIndex[i][1] + T.basisIndex[i][2]);
     }
     for (int i = 0; i <= kMaxDegree; ++i) h->count[i] = (uint32_t)T.coeffCount[i];
+    std::memcpy(h->transfer, T.transfer, sizeof T.transfer);
     hipError_t me = hipMalloc((void**)&c->dTables, sizeof(DeviceTables));
     if (me == hipSuccess) me = hipMemcpy(c->dTables, h, sizeof(DeviceTables), hipMemcpyHostToDevice);
     delete h;

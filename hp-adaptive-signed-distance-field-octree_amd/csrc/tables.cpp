@@ -104,6 +104,49 @@ double newtonSqrt(double x) {
     return g;
 }
 
+// Simplify's transfer matrices.  The integrand is a polynomial of degree <= 24: the 16-point rule is exact for it.  Nodes, weights, the
+// recurrence and the sum are kept in double-double (the rules above round theirs to double, which would leave ~1e-16 in the integral);
+// the integral then goes to long double, where the normalisation -- an exactly representable number's square root -- is applied, and
+// the product is rounded to double once: every entry is within 1 ulp of the real number.
+void transferTables(double (&out)[2][kMaxDegree + 1][kMaxDegree + 1]) {
+    constexpr int n = 16, pairs = n / 2, Q = kMaxDegree + 1;
+    DD x[n], w[n];
+    for (int k = 0; k < pairs; ++k) {
+        DD r(std::cos(M_PI * ((pairs - k) - 0.25) / (n + 0.5)));
+        DD p, dp;
+        for (int it = 0; it < 8; ++it) {
+            legendre(n, r, p, dp);
+            r = r - p / dp;
+        }
+        legendre(n, r, p, dp);
+        x[2 * k] = -r, x[2 * k + 1] = r;
+        w[2 * k] = w[2 * k + 1] = DD(2.0) / ((DD(1.0) - r * r) * dp * dp);
+    }
+    const auto all = [](const DD& t, DD (&P)[Q]) {  // P_0 .. P_12 at t
+        P[0] = DD(1.0), P[1] = t;
+        for (int k = 2; k < Q; ++k) P[k] = (DD(2.0 * k - 1.0) * t * P[k - 1] - DD(k - 1.0) * P[k - 2]) / DD(double(k));
+    };
+    for (int s = 0; s < 2; ++s) {
+        DD sum[Q][Q];
+        for (int m = 0; m < n; ++m) {
+            DD Pc[Q], Pp[Q];
+            all(x[m], Pc);
+            all((x[m] + DD(2.0 * s - 1.0)) * DD(0.5), Pp);
+            for (int i = 0; i < Q; ++i)
+                for (int j = 0; j <= i; ++j) sum[i][j] = sum[i][j] + w[m] * Pp[i] * Pc[j];
+        }
+        for (int i = 0; i < Q; ++i)
+            for (int j = 0; j < Q; ++j) {
+                long double integral = (long double)sum[i][j].hi + (long double)sum[i][j].lo;
+                // The integral is a rational whose denominator divides 2^36 lcm(1 .. 25) < 2^71: one that is not 0 is above 2^-71, and
+                // the double-double sum is within 2^-95 of it.  Below 2^-90 it is an exact 0 (T[2][0] is one).
+                if (fabsl(integral) < 0x1p-90L) integral = 0.0L;
+                const long double norm = sqrtl((long double)((2 * i + 1) * (2 * j + 1)) / 2.0L);
+                out[s][i][j] = j <= i ? (double)(norm * 0.5L * integral) : 0.0;
+            }
+    }
+}
+
 Tables* build() {
     Tables* t = new Tables();
     for (int n = 1; n <= 64; ++n) glRule(n, t->roots + glOffset(n), t->weights + glOffset(n));
@@ -133,6 +176,7 @@ Tables* build() {
                 t->basisIndex[row][2] = p - a - b;
                 ++row;
             }
+    transferTables(t->transfer);
     return t;
 }
 

@@ -27,6 +27,10 @@ struct Tables {
     uint64_t coeffCount[kMaxDegree + 1];                       // {1,4,10,20,35,56,83,120,...}
     uint64_t basisIndex[kMaxCoeffs][3];                        // graded order
     uint64_t sumToN[4 * kMaxDegree + 2];
+    // Simplify's transfer matrices (include/hpsdf.h, "Simplify"): transfer[s][i][j] = sqrt((2i+1)(2j+1)/2) * 1/2 * the integral over
+    // [-1, 1] of P_i((t + 2s - 1) / 2) P_j(t) dt, s = 0 the lower and 1 the upper half of an axis; lower-triangular, exactly 0 above
+    // the diagonal.  The L2 projection of a child's 1-D basis onto its parent's, independent of the depth.
+    double transfer[2][kMaxDegree + 1][kMaxDegree + 1];
 };
 
 const Tables& tables();  // thread-safe lazy singleton

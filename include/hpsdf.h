@@ -884,6 +884,90 @@ HPSDF_API int hpsdf_integrate_host(hpsdf_ctx* ctx, const hpsdf_tree* t, double i
 HPSDF_API int hpsdf_integrate_block(const void* block, size_t size, double iso, uint32_t depth, uint32_t samples, uint32_t max_cells,
                                     hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
 
+/* ---- Simplify: hp-coarsen a built tree within an RMS bound (no reference counterpart) ---------------------------------------------------
+ * Makes a NEW tree from a serialised one: sibling leaves are merged into their parent (h-coarsening) and top degrees are dropped
+ * (p-coarsening) wherever that keeps the result within `rms` of the source, cell by cell.  The source block is never written.  No field
+ * sample is taken: everything is computed from the coefficients, and the error is bounded, not estimated.  The result is an ordinary
+ * MemoryBlock -- hpsdf_tree_upload, the *_block entries and the reference's FromMemoryBlock / Query read it.
+ * Why coefficients suffice.  In the root's normalised frame [-0.5, 0.5]^3 a cell at depth d has volume 8^-d, and a leaf's basis -- the
+ * products of sqrt((2i+1) 2^d) P_i along each axis (NormalisedLengths, Utility.h:63-78) -- is orthonormal over its cell, and graded:
+ * the rows of degree p are a prefix of the rows of degree p + 1.  So (1) dropping rows is the L2 projection and its squared L2 error is
+ * the sum of the squares of the dropped rows; (2) the L2 projection of the polynomials of eight siblings onto one polynomial over their
+ * parent is the separable map below, whose two 13 x 13 matrices do not depend on the depth; (3) the parent's polynomial restricted to
+ * a child is the transposed map, so the projection's error is computable exactly as well.
+ * Arguments: a block that hpsdf_query_bounds_block accepts; rms finite and >= 0; flags a combination of HPSDF_SIMPLIFY_MERGE and
+ * HPSDF_SIMPLIFY_TRUNCATE (HPSDF_SIMPLIFY_DEFAULT = both).
+ *   Tables     For the lower (s = 0) and the upper (s = 1) half of an axis and 0 <= j <= i <= 12
+ *                T_s[i][j] = sqrt((2i+1)(2j+1)/2) * 1/2 * integral over [-1, 1] of P_i((t + 2s - 1) / 2) P_j(t) dt,
+ *              0 above the diagonal; computed once on the host beyond long-double accuracy (a 16-point Gauss rule, nodes, recurrence and
+ *              sum in double-double, the normalisation in long double) and rounded to double: hpsdf_simplify_transfer returns them.
+ *              sum_s T_s T_s^T = I.  Bit a of a child's index selects the upper half on axis a (CornerAABB's convention).
+ *   Entries    Entry (i, j, k) of a polynomial of degree q, i + j + k <= q, is its row in the basis's order.  A leaf of degree d stores
+ *              count[d] rows; a row it does not store counts as 0 -- the rows above its degree, and (6, 0, 0) of a degree-6 leaf, whose
+ *              count is 83 (the reference's table).
+ *   e          Every leaf carries e, a bound on the squared L2 distance between the result and the SOURCE over its cell; 0 at first.
+ *   Merge      (flag MERGE) For D = maxDepth .. 2, every interior node at depth D - 1 whose eight children are leaves -- leaves made
+ *              at the level before included -- is a candidate.  q = the largest child degree.  For the entries (a, b, c) of degree q,
+ *              over the children n = 0 .. 7 in that order, parent = parent + c_n's image, from 0.0:
+ *                V[a, j, k] = sum_{i <= a} T_sx[a][i] c_n[i, j, k];  W[a, b, k] = sum_{j <= b} T_sy[b][j] V[a, j, k];
+ *                image[a, b, c] = sum_{k <= c} T_sz[c][k] W[a, b, k]            (every sum from 0.0, its index ascending, s = T * x + s)
+ *              An entry the degree q does not store is then set to 0.  The residual is the direct one: for n = 0 .. 7 the parent's
+ *              restriction
+ *                V[a, b, k] = sum_{c = k .. q-a-b} T_sz[c][k] parent[a, b, c];  W[a, j, k] = sum_{b = j .. q-a-k} T_sy[b][j] V[a, b, k];
+ *                r_n[i, j, k] = sum_{a = i .. q-j-k} T_sx[a][i] W[a, j, k]
+ *              and x[e] = x[e] + (c_n[e] - r_n[e])^2 per entry e, from 0.0; the x[e], zero-padded to the next power of two P, are summed
+ *              by: for stride = P/2, P/4, .., 1: x[t] = x[t] + x[t + stride] for t < stride; e_step = x[0].  (Not sum |c_n|^2 - |parent|^2:
+ *              the same number in exact arithmetic, but all cancellation once e_step is below 1e-16 of the energy.)
+ *                b = (sqrt(e_step) + sqrt(((e_0 + e_1) + ..) + e_7))^2
+ *              The merge is accepted iff b <= (rms * rms) * 8^-(D-1) and b is finite (a NaN fails the comparison): the node becomes a
+ *              leaf of degree q with the parent's rows and e = b; its children are dropped.  The root stays interior: eight leaves
+ *              at depth 1 (9 nodes) are the coarsest result.
+ *   Truncate   (flag TRUNCATE) For every leaf of the result so far, of degree d at depth D: tail(d'') = the sum of the squares of its rows
+ *              from count[d''] on, formed shell by shell from the top (a shell's squares in row order from 0.0; tail = tail + shell).
+ *              For d'' = d - 1, d - 2, ..: b = (sqrt(tail(d'')) + sqrt(e))^2 with the leaf's e from the merge pass; while
+ *              b <= (rms * rms) * 8^-D and b is finite the leaf's degree becomes d'' and its e becomes b; the first d'' that fails ends it.
+ *   rms == 0   Both passes are skipped: the result is the source, re-serialised in the canonical order.
+ *   Output     The surviving nodes keep their relative order (a node's new index is its rank among the survivors, so groups of eight
+ *              siblings stay contiguous; nodes the source's root does not reach are not survivors), child_idx is remapped, a leaf's is
+ *              all-ones; boxes and depths are the source's; the coefficients lie in the order of Octree::ReallocCoeffs
+ *              (Octree.cpp:474-555), a depth-first walk with children 0 .. 7; the Config is copied unchanged.
+ * Guarantee.  Every leaf cell C of the result satisfies  integral over C of (result - source)^2 <= e_C <= rms^2 vol(C), so the RMS
+ * deviation over every leaf cell, and therefore over the root, is at most rms; the squared L2 deviation over the root is at most
+ * error_bound = the sum of e_C.  Derivation, by induction over the steps: a leaf of the source has deviation 0 = e.  A merge replaces,
+ * over the parent's cell, the current result g (within sqrt(sum e_n) of the source f in L2 over that cell, the children's cells being
+ * disjoint) by the parent's polynomial h with |g - h|^2 = e_step computed directly; |f - h| <= |f - g| + |g - h| gives b.  A truncation
+ * replaces a leaf's polynomial g by its prefix h with |g - h|^2 = tail exactly (orthonormal rows), and the same inequality applies.
+ * Each accepted b satisfies the cell's threshold, so e_C <= rms^2 vol(C) at every step.  What is outside the statement: the float64
+ * rounding of e_step, tail and the rows themselves (relative 1e-15 of the energy, not of the residual: a bound far below 1e-30 of a
+ * cell's energy means "equal to rounding").
+ * Limits, stated rather than hidden: the deviation measured is the UNWEIGHTED L2 norm -- a nearness-weighted Config is copied but
+ * plays no part --, it is a mean-square bound per cell, not a pointwise one; a source that went through the continuity post-process
+ * loses the enforced continuity wherever cells change.  Out of scope: a global error budget in place of the per-cell one; merging
+ * into a degree above the children's; re-establishing continuity afterwards.
+ * hpsdf_simplify runs on the context's device and stream (per level: simplify_candidates_kernel, one rocPRIM scan, simplify_list_kernel
+ * and simplify_merge_kernel; simplify_truncate_kernel once at the end; csrc/simplify.hip) and synchronises before it returns; *out_block
+ * comes from the context's block allocator, or malloc (the caller frees it), as for hpsdf_create.  hpsdf_simplify_block computes on the
+ * calling thread with no device (csrc/simplify_host.cpp) and always mallocs.  Both run the statements of csrc/simplify.hpp in the order
+ * written above (no multiply-add is fused) and return the same bytes and the same stats.  Blocks are accepted and refused as
+ * hpsdf_query_bounds_block does.  rms negative or not finite, unknown flag bits, NULL out_block or out_size:
+ * HPSDF_ERR_INVALID_ARGUMENT.  On any failure nothing is written and nothing stays allocated.  stats may be NULL. */
+enum { HPSDF_SIMPLIFY_MERGE = 1, HPSDF_SIMPLIFY_TRUNCATE = 2 };
+#define HPSDF_SIMPLIFY_DEFAULT (HPSDF_SIMPLIFY_MERGE | HPSDF_SIMPLIFY_TRUNCATE)
+typedef struct hpsdf_simplify_stats {
+    uint64_t nodes_in, coeffs_in, leaves_in;    /* the source, as its root reaches it */
+    uint64_t nodes_out, coeffs_out, leaves_out; /* the result */
+    uint64_t merges;      /* accepted merges, those whose leaf was merged again included */
+    uint64_t truncations; /* leaves whose degree the truncation pass lowered */
+    uint64_t levels;      /* levels of the merge pass that had a candidate */
+    double error_bound;   /* the sum of e over the result's leaves: bounds the squared L2 deviation over the root */
+    double max_cell_rms;  /* the largest sqrt(e / vol) over the result's leaves; <= rms */
+} hpsdf_simplify_stats;
+HPSDF_API int hpsdf_simplify(hpsdf_ctx* ctx, const void* block, size_t size, double rms, uint32_t flags, void** out_block, size_t* out_size,
+                             hpsdf_simplify_stats* stats);
+HPSDF_API int hpsdf_simplify_block(const void* block, size_t size, double rms, uint32_t flags, void** out_block, size_t* out_size,
+                                   hpsdf_simplify_stats* stats);
+HPSDF_API int hpsdf_simplify_transfer(double out[2][13][13]);
+
 /* ---- Create: Octree::Create under the canonical round schedule ---------------
  * (Octree.cpp:312-352, 194-309, 558-659, 804-856, 1007-1093; schedule: DESIGN.md)
  *

@@ -748,6 +748,42 @@ class Octree {
         return r;
     }
 
+    /// A NEW octree within rms_ of this one, leaf cell by leaf cell, in the root-normalised L2 sense (no reference counterpart;
+    /// include/hpsdf.h, "Simplify"): sibling leaves merged into their parent (HPSDF_SIMPLIFY_MERGE) and top degrees dropped
+    /// (HPSDF_SIMPLIFY_TRUNCATE) from the coefficients alone -- no field is sampled --, every result cell C with
+    /// integral_C (result - this)^2 <= rms_^2 vol(C).  This octree is not modified; the result has this one's settings.  host_: computed on
+    /// the calling thread (hpsdf_simplify_block; the same bytes, and no device is touched until the result is queried).
+    Octree Simplify(f64 rms_, uint32_t flags_ = HPSDF_SIMPLIFY_DEFAULT, hpsdf_simplify_stats* stats_ = nullptr, bool host_ = false) const {
+        if (!block_) throw Error(HPSDF_ERR_STATE, "Simplify on an empty octree");
+        void* blk = nullptr;
+        size_t sz = 0;
+        if (host_) {
+            check(hpsdf_simplify_block(block_, size_, rms_, flags_, &blk, &sz, stats_));
+        } else {
+            ensureCtx();
+            check(hpsdf_simplify(ctx_, block_, size_, rms_, flags_, &blk, &sz, stats_));
+        }
+        Octree o;
+        o.block_ = blk;  // (malloc'd: this header installs no block allocator; o frees it whatever happens next)
+        o.size_ = sz;
+        o.copySettings(*this);
+        o.mirrorPending_.store(true, std::memory_order_release);  // (deviceTree())
+        return o;
+    }
+    /// The same from a serialised block, on the calling thread: no octree and no device is needed to make the result (it is uploaded
+    /// when it is first queried).  The block stays the caller's.
+    static Octree SimplifyBlock(MemoryBlock octBlock_, f64 rms_, uint32_t flags_ = HPSDF_SIMPLIFY_DEFAULT, hpsdf_simplify_stats* stats_ = nullptr) {
+        void* blk = nullptr;
+        size_t sz = 0;
+        check(hpsdf_simplify_block(octBlock_.ptr, octBlock_.size, rms_, flags_, &blk, &sz, stats_));
+        Octree o;
+        o.block_ = blk;
+        o.size_ = sz;
+        o.readConfig();
+        o.mirrorPending_.store(true, std::memory_order_release);
+        return o;
+    }
+
     /// Returns the aabb of the root node   (Octree.h:81)
     Eigen::AlignedBox3f GetRootAABB() const { return config_.root; }
 
@@ -790,6 +826,7 @@ class Octree {
         if (mirrorPending_.load(std::memory_order_acquire)) {
             std::lock_guard<std::mutex> guard(mirrorLock_);
             if (mirrorPending_.load(std::memory_order_relaxed)) {
+                ensureCtx();  // (Simplify's result has none until here)
                 check(hpsdf_tree_upload(ctx_, block_, size_, &tree_));
                 mirrorPending_.store(false, std::memory_order_release);
             }
