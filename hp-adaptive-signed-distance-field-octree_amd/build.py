@@ -34,6 +34,10 @@ FLAGS += os.environ.get("HPSDF_EXTRA_FLAGS", "").split()
 # compiler gives them AGPR results and copies all of them to VGPRs and back around every step of the k-loop
 # (2 x 8 moves per tile and step, and a wait for each result)
 FILE_FLAGS = {"fit_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+# the units that include leaf_jet.hpp: it asks for full unrolling of loops whose trip count only its compile-time degrees have, and the
+# any-degree instantiation's "loop not unrolled" remark is expected there; every other unit keeps that warning
+for _s in ("query_gradient.hip", "query_hessian.hip", "project.hip", "cast_rays.hip", "surface_dual.hip", "host_query.cpp"):
+    FILE_FLAGS[_s] = ["-Wno-pass-failed"]
 
 
 def hipcc():

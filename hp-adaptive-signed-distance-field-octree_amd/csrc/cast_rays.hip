@@ -1,5 +1,5 @@
 // CastRays: the first crossing of each ray with the level set {Query = iso} (include/hpsdf.h, "CastRays"; the walk's statements are
-// ray_cast.hpp's castRay, the field evaluation is QueryGradient's trueGradientPoint, true_gradient_point.hpp).
+// ray_cast.hpp's castRay, the field evaluation is QueryGradient's trueGradientPoint, jet_point.hpp).
 //
 // One lane per ray: 56 bytes read (origin, direction, t_max), 1 written, plus whichever of the optional outputs are asked for
 // (8 + 24 + 8 + 24 + 2 + 2), plus one leaf's row per field evaluation and one descent (8-byte records) per leaf visited.
@@ -19,11 +19,10 @@
 #include <cstdint>
 
 #include "device_types.hpp"
+#include "jet_point.hpp"
 #include "launch.hpp"
 #include "leaf_eval.hpp"
-#include "leaf_gradient.hpp"
 #include "ray_cast.hpp"
-#include "true_gradient_point.hpp"
 
 namespace hpsdf {
 

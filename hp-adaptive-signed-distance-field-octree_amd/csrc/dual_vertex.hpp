@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "../../include/hpsdf.h"
+#include "leaf_jet.hpp"
 
 namespace hpsdf {
 
@@ -28,7 +29,6 @@ struct DualNormal {
     double a[3][3], b[3];
 };
 
-__host__ __device__ inline double dualSum3(double a, double b, double c, int leftAssoc) { return leftAssoc ? (a + b) + c : a + (b + c); }
 __host__ __device__ inline bool dualFinite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN
 
 __host__ __device__ inline void dualClear(DualNormal& N, double (&sum)[3]) {
@@ -50,7 +50,7 @@ __host__ __device__ inline void dualMean(const double (&sum)[3], uint32_t k, dou
 __host__ __device__ inline void dualAccumulate(const double* p, double f, const double* g, const double (&m)[3], double iso, int leftAssoc,
                                                DualNormal& N) {
     const double d[3] = {p[0] - m[0], p[1] - m[1], p[2] - m[2]};
-    const double r = (iso - f) + dualSum3(g[0] * d[0], g[1] * d[1], g[2] * d[2], leftAssoc);
+    const double r = (iso - f) + sum3(g[0] * d[0], g[1] * d[1], g[2] * d[2], leftAssoc);
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) N.a[i][j] = N.a[i][j] + g[i] * g[j];
         N.b[i] = N.b[i] + g[i] * r;
@@ -108,7 +108,7 @@ __host__ __device__ inline uint32_t dualSolve(DualNormal& N, const double (&m)[3
         const double thr = tau * lmax;
         for (int i = 0; i < 3; ++i) {
             if (!(l[i] > thr && l[i] > 0.0)) continue;
-            const double w = dualSum3(v[0][i] * N.b[0], v[1][i] * N.b[1], v[2][i] * N.b[2], leftAssoc) / l[i];
+            const double w = sum3(v[0][i] * N.b[0], v[1][i] * N.b[1], v[2][i] * N.b[2], leftAssoc) / l[i];
             for (int a = 0; a < 3; ++a) x[a] = x[a] + v[a][i] * w;
             ++rank;
         }

@@ -23,8 +23,7 @@
 #include "edge_vertex.hpp"
 #include "integrate.hpp"
 #include "lattice_check.hpp"
-#include "leaf_gradient.hpp"
-#include "leaf_hessian.hpp"
+#include "leaf_jet.hpp"
 #include "ray_cast.hpp"
 #include "runtime.hpp"
 #include "tables.hpp"
@@ -78,32 +77,22 @@ inline bool descend(const hpsdf_tree& t, const double* xyz, Leaf& L) {
     return true;
 }
 
+// the leaf's polynomial with its derivatives up to ORDER (leaf_jet.hpp), from the process's tables
+template <int ORDER>
+inline double leafValue(const Leaf& L, GradOut<ORDER> gu, HessOut<ORDER> hu) {
+    const Tables& T = tables();
+    return leafJet<ORDER>(
+        L.co, AnyDegree{L.degree}, (int)T.coeffCount[L.degree], L.u, L.depth, &T.normalisedLengths[0][0], &T.recurrence[0][0],
+        [&T](int r, int k) { return (int)T.basisIndex[r][k]; }, gu, hu);
+}
+
 }  // namespace
 
 // Octree::Query + FApprox (Octree.cpp:662-702, 859-901)
 double hostQueryPoint(const hpsdf_tree& t, const double* xyz) {
     Leaf L;
     if (!descend(t, xyz, L)) return DBL_MAX;
-    const Tables& T = tables();
-    double tab[3][13];
-    for (int a = 0; a < 3; ++a) {
-        tab[a][0] = T.normalisedLengths[0][L.depth];
-        double m2 = 0.0, m1 = 1.0;
-        for (int j = 1; j <= L.degree; ++j) {
-            const double l = T.recurrence[j][0] * L.u[a] * m1 - T.recurrence[j][1] * m2;
-            m2 = m1, m1 = l;
-            tab[a][j] = l * T.normalisedLengths[j][L.depth];
-        }
-    }
-    double f = 0.0;
-    const int n = (int)T.coeffCount[L.degree];
-    for (int i = 0; i < n; ++i) {
-        double lp = tab[0][T.basisIndex[i][0]];
-        lp = lp * tab[1][T.basisIndex[i][1]];
-        lp = lp * tab[2][T.basisIndex[i][2]];
-        f = f + L.co[i] * lp;
-    }
-    return f;
+    return leafValue<0>(L, NoOutput{}, NoOutput{});
 }
 
 // Octree::QueryWithGradient + FApproxWithGradient (Octree.cpp:749-789, 904-985).  Outside the root: *out = DBL_MAX, grad untouched.
@@ -139,12 +128,7 @@ void hostQueryPointWithGradient(const hpsdf_tree& t, const double* xyz, double* 
         }
         g[k] = (p1 - m1) / (2.0 * eps);
     }
-    const double g2[3] = {g[0] * g[0], g[1] * g[1], g[2] * g[2]};
-    const double z = leftAssoc ? (g2[0] + g2[1]) + g2[2] : g2[0] + (g2[1] + g2[2]);  // Eigen normalize()
-    if (z > 0.0) {
-        const double nrm = std::sqrt(z);
-        g[0] = g[0] / nrm, g[1] = g[1] / nrm, g[2] = g[2] / nrm;
-    }
+    unitGradient(g, leftAssoc);  // Eigen normalize()
     double f = 0.0;  // :972-984
     for (int r = 0; r < nc; ++r) {
         double lp = Lg[T.basisIndex[r][0]][0][0];
@@ -201,7 +185,7 @@ bool hostQueryRay(const hpsdf_tree& t, const double* origin, const double* dir, 
 namespace {
 
 // QueryGradient (include/hpsdf.h): Query's descent, then the value and the gradient of the leaf's polynomial with the statements the
-// kernels run (leaf_gradient.hpp; query_gradient.hip).  Outside the root: DBL_MAX and three quiet NaNs.
+// kernels run (leaf_jet.hpp; query_gradient.hip).  Outside the root: DBL_MAX and three quiet NaNs.
 void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad) {
     Leaf L;
     if (!descend(t, xyz, L)) {
@@ -209,29 +193,23 @@ void hostQueryPointTrueGradient(const hpsdf_tree& t, const double* xyz, bool uni
         grad[0] = grad[1] = grad[2] = std::numeric_limits<double>::quiet_NaN();
         return;
     }
-    const Tables& T = tables();
     double gu[3], g[3];
-    const double f = leafTrueGradient(
-        L.co, L.degree, (int)T.coeffCount[L.degree], L.u, L.depth, &T.normalisedLengths[0][0], &T.recurrence[0][0],
-        [&T](int r, int k) { return (int)T.basisIndex[r][k]; }, gu);
+    const double f = leafValue<1>(L, gu, NoOutput{});
     finishTrueGradient(gu, L.depth, t.dev.rootInvSizes, unit, leftAssoc, g);
     if (out) *out = f;
     grad[0] = g[0], grad[1] = g[1], grad[2] = g[2];
 }
 
 // QueryHessian (include/hpsdf.h): Query's descent, then value, gradient, second derivative and curvature with the statements the kernels
-// run (leaf_hessian.hpp; query_hessian.hip).  Every output may be null.  Outside the root: DBL_MAX and quiet NaNs.
+// run (leaf_jet.hpp; query_hessian.hip).  Every output may be null.  Outside the root: DBL_MAX and quiet NaNs.
 [[gnu::noinline]] void hostQueryPointHessian(const hpsdf_tree& t, const double* xyz, bool unit, int leftAssoc, double* out, double* grad,
                                              double* hess, double* curv) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     double f = DBL_MAX, g[3] = {nan, nan, nan}, H[6] = {nan, nan, nan, nan, nan, nan}, k[2] = {nan, nan};
     Leaf L;
     if (descend(t, xyz, L)) {
-        const Tables& T = tables();
         double gu[3], hu[6];
-        f = leafHessian(
-            L.co, L.degree, (int)T.coeffCount[L.degree], L.u, L.depth, &T.normalisedLengths[0][0], &T.recurrence[0][0],
-            [&T](int r, int c) { return (int)T.basisIndex[r][c]; }, gu, hu);
+        f = leafValue<2>(L, gu, hu);
         finishTrueGradient(gu, L.depth, t.dev.rootInvSizes, false, leftAssoc, g);
         finishHessian(hu, L.depth, t.dev.rootInvSizes, H);
         if (curv) levelSetCurvature(g, H, leftAssoc, k);

@@ -1,6 +1,6 @@
 // ProjectToSurface: Newton's iteration x <- x - (f(x) - iso) grad f(x) / |grad f(x)|^2 onto the level set {Query = iso}, run to a
-// tolerance on the device (include/hpsdf.h, "ProjectToSurface"; the loop's statements are leaf_gradient.hpp's projectStep, the field
-// evaluation is QueryGradient's trueGradientPoint, true_gradient_point.hpp).
+// tolerance on the device (include/hpsdf.h, "ProjectToSurface"; the loop's statements are leaf_jet.hpp's projectStep, the field
+// evaluation is QueryGradient's trueGradientPoint, jet_point.hpp).
 //
 // One lane per point: 24 bytes read, 24 written, plus whichever of the optional outputs are asked for (8 + 24 + 1 + 1), plus one leaf's
 // row per field evaluation.
@@ -18,10 +18,9 @@
 #include <cstdint>
 
 #include "device_types.hpp"
+#include "jet_point.hpp"
 #include "launch.hpp"
 #include "leaf_eval.hpp"
-#include "leaf_gradient.hpp"
-#include "true_gradient_point.hpp"
 
 namespace hpsdf {
 

@@ -1,12 +1,12 @@
 // QueryGradient: the value of a tree at points and the gradient of the polynomial that value comes from (include/hpsdf.h,
-// "QueryGradient"; the arithmetic is leaf_gradient.hpp's).  QueryWithGradient -- the reference's per-axis shortcut -- stays in kernels.hip.
+// "QueryGradient"; the arithmetic is leaf_jet.hpp's).  QueryWithGradient -- the reference's per-axis shortcut -- stays in kernels.hip.
 //
 // One lane per point: 24 bytes read, 8 + 24 written (non-temporally, as Query's results leave), plus the leaf's row.
 //   query_true_gradient_top_kernel   trees whose leaves all sit in the top table with degree <= 2 (what the default thresholds produce):
 //                                    the wave fetches the points' 128-byte lines cooperatively into LDS, as query_kernel does;
 //   query_true_gradient_kernel<MAXP> any tree: queryPoint's descent (top table, then the walk), the leaf's coefficients lane by lane;
 //   query_true_gradient_few_kernel   the same for a handful of points in workgroups of one wave.
-// The per-point routine of the last two, trueGradientPoint, lives in true_gradient_point.hpp (project.hip runs it too).
+// The per-point routine of the last two, trueGradientPoint, is jet_point.hpp's jetPoint at order 1 (project.hip runs it too).
 // Rows of points outside the root (or with a NaN coordinate) are DBL_MAX and three quiet NaNs.
 //
 // Built with -ffp-contract=off like every other unit: the host versions (host_query.cpp) give the same bits.
@@ -16,10 +16,9 @@
 #include <cstdint>
 
 #include "device_types.hpp"
+#include "jet_point.hpp"
 #include "launch.hpp"
 #include "leaf_eval.hpp"
-#include "leaf_gradient.hpp"
-#include "true_gradient_point.hpp"
 
 namespace hpsdf {
 
@@ -133,11 +132,11 @@ __global__ __launch_bounds__(256) void query_true_gradient_top_kernel(TreeDev t,
             const double u[3] = {(p3[0] - c3[0]) * s, (p3[1] - c3[1]) * s, (p3[2] - c3[2]) * s};
             double gu[3];
             if (hdr.y == 2u)
-                f = leafTrueGradientVals<2>(cv, u, topDepth, sNl, sRec, gu);
+                f = leafJetVals<1, 2>(cv, u, topDepth, sNl, sRec, gu, NoOutput{});
             else if (hdr.y == 1u)
-                f = leafTrueGradientVals<1>(cv, u, topDepth, sNl, sRec, gu);
+                f = leafJetVals<1, 1>(cv, u, topDepth, sNl, sRec, gu, NoOutput{});
             else
-                f = leafTrueGradientVals<0>(cv, u, topDepth, sNl, sRec, gu);
+                f = leafJetVals<1, 0>(cv, u, topDepth, sNl, sRec, gu, NoOutput{});
             finishTrueGradient(gu, topDepth, t.rootInvSizes, unit, t.leftAssoc, g);
         }
         if (valid) storeGradientRow(i, f, g, out, grad);

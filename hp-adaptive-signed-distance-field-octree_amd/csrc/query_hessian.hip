@@ -1,5 +1,5 @@
 // QueryHessian: the value of a tree at points, the gradient and the second derivative of the polynomial that value comes from, and the
-// mean and Gaussian curvature of its level set (include/hpsdf.h, "QueryHessian"; the arithmetic is leaf_hessian.hpp's).
+// mean and Gaussian curvature of its level set (include/hpsdf.h, "QueryHessian"; the arithmetic is leaf_jet.hpp's).
 //
 // One lane per point: 24 bytes read, up to 8 + 24 + 48 + 16 written (non-temporally, and only the outputs asked for), plus the leaf's row.
 //   query_hessian_kernel<MAXP>       any tree: hessianPoint's descent (top table, then the walk), the leaf's coefficients lane by lane;
@@ -15,10 +15,9 @@
 #include <cstdint>
 
 #include "device_types.hpp"
-#include "hessian_point.hpp"
+#include "jet_point.hpp"
 #include "launch.hpp"
 #include "leaf_eval.hpp"
-#include "leaf_hessian.hpp"
 
 namespace hpsdf {
 

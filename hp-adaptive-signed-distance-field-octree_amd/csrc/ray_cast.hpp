@@ -19,7 +19,7 @@
 #include <cstdint>
 
 #include "../../include/hpsdf.h"
-#include "leaf_gradient.hpp"
+#include "leaf_jet.hpp"
 
 namespace hpsdf {
 
@@ -48,8 +48,6 @@ __host__ __device__ inline double castBelow(double v) {
 }
 
 __host__ __device__ inline bool castFinite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN
-
-__host__ __device__ inline double castSum3(double a, double b, double c, int leftAssoc) { return leftAssoc ? (a + b) + c : a + (b + c); }
 
 // step 1: a ray the walk can take
 __host__ __device__ inline bool castValid(const double* o, const double* d, double tMax) {
@@ -208,7 +206,7 @@ __host__ __device__ inline void castRay(Field& F, const double* rootCentre, cons
             } else {
                 bb = te, fb = f, gb[0] = g[0], gb[1] = g[1], gb[2] = g[2];
             }
-            c = te, rc = rm, sc = castSum3(g[0] * d[0], g[1] * d[1], g[2] * d[2], leftAssoc);
+            c = te, rc = rm, sc = sum3(g[0] * d[0], g[1] * d[1], g[2] * d[2], leftAssoc);
             halved = (bb - ba) <= 0.5 * w;
             ++k;
         } else {
@@ -230,7 +228,7 @@ __host__ __device__ inline void castRay(Field& F, const double* rootCentre, cons
                 walk = true;
             } else if ((prev < 0.0) != (cur < 0.0)) {
                 ba = tPrev, ra = prev, bb = te, fb = f, gb[0] = g[0], gb[1] = g[1], gb[2] = g[2];
-                c = te, rc = cur, sc = castSum3(g[0] * d[0], g[1] * d[1], g[2] * d[2], leftAssoc);
+                c = te, rc = cur, sc = sum3(g[0] * d[0], g[1] * d[1], g[2] * d[2], leftAssoc);
                 halved = true, k = 0;
                 phase = kRefine;
             } else {

@@ -23,11 +23,10 @@
 
 #include "device_types.hpp"
 #include "dual_vertex.hpp"
+#include "jet_point.hpp"
 #include "launch.hpp"
 #include "leaf_eval.hpp"
-#include "leaf_gradient.hpp"
 #include "surface_common.hpp"
-#include "true_gradient_point.hpp"
 
 namespace hpsdf {
 

@@ -1,4 +1,4 @@
-"""An extended-precision reference for QueryGradient (include/hpsdf.h; csrc/leaf_gradient.hpp) on top of hiprec.Block, and a
+"""An extended-precision reference for QueryGradient (include/hpsdf.h; csrc/leaf_jet.hpp) on top of hiprec.Block, and a
 worst-case bound per gradient component derived from the order of the operations, in the manner of hiprec.py section 3.
 
 What the product forms in float64 before the arithmetic under test -- the root remap (hiprec.Block.to_unit), the descent

@@ -1,4 +1,4 @@
-"""An extended-precision reference for QueryHessian (include/hpsdf.h; csrc/leaf_hessian.hpp) on top of hiprec.Block, and a worst-case
+"""An extended-precision reference for QueryHessian (include/hpsdf.h; csrc/leaf_jet.hpp) on top of hiprec.Block, and a worst-case
 bound per Hessian entry derived from the order of the operations, in the manner of hiprec_gradient.py.
 
 What the product forms in float64 before the arithmetic under test -- the root remap (hiprec.Block.to_unit), the descent
