@@ -194,6 +194,12 @@ _SIGNATURES = {
     "hpsdf_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_integrate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_integrate_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_integrate_pair_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_integrate_pair_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_integrate_pair_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_double, C.c_double, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_simplify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     "hpsdf_simplify_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     "hpsdf_simplify_transfer": (C.c_int, [C.c_void_p]),
@@ -807,6 +813,16 @@ class DeviceTree:
         fn = lib().hpsdf_integrate_host if host else lib().hpsdf_integrate_device
         return _integrate(lambda *rest: fn(self.ctx.handle, self.handle, *rest), iso, depth, samples, max_cells, cells)
 
+    def integrate_pair(self, other, op, pose=None, iso_a=0.0, iso_b=0.0, depth=8, samples=2, max_cells=1 << 24, max_leaves=256, cells=False,
+                       host=False):
+        """IntegratePair (include/hpsdf.h): Integrate over this tree (A) with every cell also classified against `other` (B) under
+        pose (12 doubles [M | t], see pose(); None: the identity) -> PairIntegral for op = PAIR_INTERSECTION, PAIR_UNION or
+        PAIR_DIFFERENCE of {Query_A < iso_a} and {x : Query_B(M x + t) < iso_b}, over A's root and in A's frame.  host=True: on the
+        calling thread from the trees' host copies (the same bits)."""
+        fn = lib().hpsdf_integrate_pair_host if host else lib().hpsdf_integrate_pair_device
+        return _integrate_pair(lambda *rest: fn(self.ctx.handle, self.handle, other.handle, *rest), op, pose, iso_a, iso_b, depth, samples,
+                               max_cells, max_leaves, cells)
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1278,6 +1294,13 @@ class Octree:
             raise HpsdfError(6, "Query on an empty octree")
         return self._tree.integrate(iso, depth, samples, max_cells, cells)
 
+    def IntegratePair(self, other, op, pose=None, iso_a=0.0, iso_b=0.0, depth=8, samples=2, max_cells=1 << 24, max_leaves=256, cells=False):
+        """Volume bounds and moments of the intersection, union or difference (op: PAIR_*) of this solid with other's under a pose
+        (DeviceTree.integrate_pair) -> PairIntegral, in this octree's frame; .disjoint / .overlapping are proofs for the intersection."""
+        if self._tree is None or other._tree is None:
+            raise HpsdfError(ERR_STATE, "IntegratePair on an empty octree")
+        return self._tree.integrate_pair(other._tree, op, pose, iso_a, iso_b, depth, samples, max_cells, max_leaves, cells)
+
     def Simplify(self, rms, merge=True, truncate=True, stats=False):
         """A NEW Octree on the same context whose field is within `rms` of this one's in the root-normalised L2 sense, leaf cell by leaf
         cell (include/hpsdf.h, "Simplify"): sibling leaves merged into their parent, top degrees dropped, from the coefficients alone.
@@ -1529,6 +1552,48 @@ def integrate_block(block, iso=0.0, depth=8, samples=2, max_cells=1 << 24, cells
     """hpsdf_integrate_block: DeviceTree.integrate's result from a serialised block on the calling thread (no device)."""
     buf = bytes(block)
     return _integrate(lambda *rest: lib().hpsdf_integrate_block(buf, len(buf), *rest), iso, depth, samples, max_cells, cells)
+
+
+PAIR_INTERSECTION, PAIR_UNION, PAIR_DIFFERENCE = 0, 1, 2  # HPSDF_PAIR_*: the operation of IntegratePair
+
+
+def pose(R=None, t=None):
+    """The 12 doubles [M | t] of IntegratePair's pose, row-major, from a 3 x 3 matrix R (None: the identity) and a translation t (None:
+    zero): a point x of A's frame is R x + t in B's.  pose(None) is the identity."""
+    out = np.zeros((3, 4))
+    out[:, :3] = np.eye(3) if R is None else np.asarray(R, np.float64).reshape(3, 3)
+    if t is not None:
+        out[:, 3] = np.asarray(t, np.float64).reshape(3)
+    return np.ascontiguousarray(out.reshape(12))
+
+
+class PairIntegral(Integral):
+    """Integral of an IntegratePair call, with the two proofs the enclosure gives for the intersection: disjoint (volume_hi == 0: no
+    point of A's root is in both solids) and overlapping (volume_lo > 0: the solids interfere)."""
+
+    @property
+    def disjoint(self):
+        return self.status != INTEGRATE_NOT_FINITE and self.unit_volume_hi == 0.0
+
+    @property
+    def overlapping(self):
+        return self.status != INTEGRATE_NOT_FINITE and self.unit_volume_lo > 0.0
+
+
+def _integrate_pair(call, op, pose_, iso_a, iso_b, depth, samples, max_cells, max_leaves, cells):
+    """call(op, pose, iso_a, iso_b, depth, samples, max_cells, max_leaves, out, out_cells, out_n_cells) -> PairIntegral"""
+    P = pose() if pose_ is None else np.ascontiguousarray(np.asarray(pose_, np.float64).reshape(12))
+    r = _integrate(lambda iso, *rest: call(_max_iter(op), P.ctypes.data_as(C.c_void_p), iso, float(iso_b), *rest[:3], _max_iter(max_leaves), *rest[3:]),
+                   iso_a, depth, samples, max_cells, cells)
+    r.__class__ = PairIntegral
+    return r
+
+
+def integrate_pair_block(block_a, block_b, op, pose=None, iso_a=0.0, iso_b=0.0, depth=8, samples=2, max_cells=1 << 24, max_leaves=256, cells=False):
+    """hpsdf_integrate_pair_block: DeviceTree.integrate_pair's result from two serialised blocks on the calling thread (no device)."""
+    a, b = bytes(block_a), bytes(block_b)
+    return _integrate_pair(lambda *rest: lib().hpsdf_integrate_pair_block(a, len(a), b, len(b), *rest), op, pose, iso_a, iso_b, depth, samples,
+                           max_cells, max_leaves, cells)
 
 
 SIMPLIFY_MERGE, SIMPLIFY_TRUNCATE = 1, 2  # HPSDF_SIMPLIFY_*

@@ -9,6 +9,7 @@
 #include "block.hpp"
 #include "host_call.hpp"
 #include "integrate.hpp"
+#include "integrate_pair.hpp"
 #include "launch.hpp"
 #include "ray_cast.hpp"
 #include "runtime.hpp"
@@ -496,6 +497,47 @@ int hpsdf_integrate_host(hpsdf_ctx* ctx, const hpsdf_tree* t, double iso, uint32
     if (const int hc = t->boundHostCopies(ctx)) return hc;
     const IntegrateArgs a{iso, depth, samples, maxCells};
     return hostIntegrate(clsTreeOnHost(t), t->hRecs.size(), a, out, outCells, outCount);
+    HPSDF_CATCH
+}
+
+// IntegratePair (include/hpsdf.h): Integrate over A with every cell also classified against B under a pose (integrate_pair.hip,
+// integrate_pair.hpp, integrate_pair_host.cpp)
+int hpsdf_integrate_pair_device(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree* tB, uint32_t op, const double pose[12], double isoA,
+                                double isoB, uint32_t depth, uint32_t samples, uint32_t maxCells, uint32_t maxLeaves, hpsdf_integral* out,
+                                hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = pairArgumentError(op, pose, isoA, isoB, depth, samples, maxCells, maxLeaves, out, outCells, outCount)) return rc;
+    if (!tA || !tB) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (tA->device != tB->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_integrate_pair: the two trees live on different devices");
+    if (const int rc = treeOnContext(ctx, tA)) return rc;
+    if (const int rc = tA->boundConsts(ctx)) return rc;
+    if (const int rc = tB->boundConsts(ctx)) return rc;
+    if (const int rc = tA->integrateLeaves(ctx)) return rc;
+    const ClsTree ctA = clsTreeOnDevice(tA), ctB = clsTreeOnDevice(tB);
+    const PairArgs p = pairArgs(ctA, op, pose, isoA, isoB, maxLeaves);
+    const IntegrateArgs a{isoA, depth, samples, maxCells};
+    return integratePairOnDevice(ctx, ctA, ctB, std::max(tA->maxDegree, tB->maxDegree), tA->dLeafCells, tA->nLeafCells, p, a, out, outCells, outCount);
+    HPSDF_CATCH
+}
+
+int hpsdf_integrate_pair_host(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree* tB, uint32_t op, const double pose[12], double isoA,
+                              double isoB, uint32_t depth, uint32_t samples, uint32_t maxCells, uint32_t maxLeaves, hpsdf_integral* out,
+                              hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = pairArgumentError(op, pose, isoA, isoB, depth, samples, maxCells, maxLeaves, out, outCells, outCount)) return rc;
+    if (!tA || !tB) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (tA->device != tB->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_integrate_pair: the two trees live on different devices");
+    if (tA->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    for (const hpsdf_tree* t : {tA, tB}) {
+        if (const int hc = t->hostCopies()) return hc;
+        if (const int hc = t->boundHostCopies(ctx)) return hc;
+    }
+    const ClsTree ctA = clsTreeOnHost(tA), ctB = clsTreeOnHost(tB);
+    const PairArgs p = pairArgs(ctA, op, pose, isoA, isoB, maxLeaves);
+    const IntegrateArgs a{isoA, depth, samples, maxCells};
+    return hostIntegratePair(ctA, tA->hRecs.size(), ctB, p, a, out, outCells, outCount);
     HPSDF_CATCH
 }
 

@@ -393,68 +393,23 @@ int boundsArgumentError(uint32_t subdiv, uint32_t maxLeaves, size_t n, const voi
     return HPSDF_OK;
 }
 
-// Integrate (include/hpsdf.h) on the calling thread: integrateLevels (integrate.hpp) over two host lists, with Query's leaf evaluation --
-// the statements of the kernels of integrate.hip, the rows reduced by the same rule.
+// Integrate (include/hpsdf.h) on the calling thread: integrateLevels over host lists (integrate.hpp, HostIntegrateLists), with Query's leaf
+// evaluation -- the statements of the kernels of integrate.hip, the rows reduced by the same rule.
 namespace {
 
-struct HostIntegrateLists {
+struct HostIntegrateCells {
     const ClsTree& t;
     const IntegrateArgs& a;
     HostEval eval;
-    std::vector<IntegrateCell> cur, next;
-    std::vector<uint8_t> split;
-    std::vector<double> rows;
-
-    int classify(int level, uint32_t n, uint32_t* nSplit, bool* finite) {
-        split.assign(n, 0);
-        uint32_t count = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            bool ok = true;
-            IntegrateCell& c = cur[i];
-            c.cls = (uint8_t)integrateCellClass(t, c, level, a.iso, eval, &ok);
-            if (!ok) *finite = false;
-            split[i] = c.cls == 0u && c.depth < a.depth;
-            count += split[i];
-        }
-        *nSplit = count;
-        return HPSDF_OK;
-    }
-
-    int contribute(int level, uint32_t n, uint32_t nSplit, std::vector<IntegrateCell>* cells, double (&T)[kIntRow]) {
-        next.clear();
-        next.reserve(8 * (size_t)nSplit);
-        rows.clear();
-        double x[kIntBlock][kIntRow];
-        for (uint32_t b = 0; b < n; b += kIntBlock) {
-            std::memset(x, 0, sizeof x);
-            for (uint32_t i = b; i < n && i < b + kIntBlock; ++i) {
-                const IntegrateCell& c = cur[i];
-                if (nSplit != 0 && split[i]) {
-                    for (uint32_t ch = 0; ch < 8u; ++ch) next.push_back(integrateChild(c, ch));
-                    continue;
-                }
-                integrateCellRow(t, c, level, a.iso, a.samples, eval, x[i - b]);
-                if (cells) cells->push_back(c);
-            }
-            integrateBlockTree(x);
-            rows.insert(rows.end(), x[0], x[0] + kIntRow);
-        }
-        integrateReduceRows(rows, T);
-        cur.swap(next);
-        return HPSDF_OK;
-    }
+    uint32_t cls(const IntegrateCell& c, int level, bool* finite) { return integrateCellClass(t, c, level, a.iso, eval, finite); }
+    void row(const IntegrateCell& c, int level, double (&row)[kIntRow]) { integrateCellRow(t, c, level, a.iso, a.samples, eval, row); }
 };
 
 }  // namespace
 
 int hostIntegrate(const ClsTree& t, size_t nNodes, const IntegrateArgs& a, hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount) {
-    HostIntegrateLists L{t, a, HostEval{&tables()}, {}, {}, {}, {}};
-    integrateLeafCells(t.nodes, nNodes, L.cur);
-    IntegrateSums S;
-    if (const int rc = integrateLevels(L, a, (uint32_t)L.cur.size(), outCells != nullptr, S)) return rc;
-    hpsdf_integral r;
-    integrateResult(S, t.rootCentre, t.rootInvSizes, a.samples, &r);
-    return integrateHandOver(S, r, out, outCells, outCount);
+    HostIntegrateCells cells{t, a, HostEval{&tables()}};
+    return hostIntegrateLists(cells, t, nNodes, a, out, outCells, outCount);
 }
 
 // what hpsdf_integrate_* reject before anything runs (0: fine)

@@ -274,6 +274,69 @@ inline int integrateHandOver(const IntegrateSums& S, const hpsdf_integral& r, hp
     return HPSDF_OK;
 }
 
+// integrateLevels' lists on the calling thread.  Cells gives a cell's class and a final cell's row: cls(c, level, &finite), row(c, level, row)
+// (Integrate's: host_query.cpp; IntegratePair's: integrate_pair_host.cpp).
+template <class Cells>
+struct HostIntegrateLists {
+    Cells& cells;
+    uint32_t maxDepth;
+    std::vector<IntegrateCell> cur, next;
+    std::vector<uint8_t> split;
+    std::vector<double> rows;
+
+    int classify(int level, uint32_t n, uint32_t* nSplit, bool* finite) {
+        split.assign(n, 0);
+        uint32_t count = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            bool ok = true;
+            IntegrateCell& c = cur[i];
+            c.cls = (uint8_t)cells.cls(c, level, &ok);
+            if (!ok) *finite = false;
+            split[i] = c.cls == 0u && c.depth < maxDepth;
+            count += split[i];
+        }
+        *nSplit = count;
+        return HPSDF_OK;
+    }
+
+    int contribute(int level, uint32_t n, uint32_t nSplit, std::vector<IntegrateCell>* finals, double (&T)[kIntRow]) {
+        next.clear();
+        next.reserve(8 * (size_t)nSplit);
+        rows.clear();
+        double x[kIntBlock][kIntRow];
+        for (uint32_t b = 0; b < n; b += kIntBlock) {
+            std::memset(x, 0, sizeof x);
+            for (uint32_t i = b; i < n && i < b + kIntBlock; ++i) {
+                const IntegrateCell& c = cur[i];
+                if (nSplit != 0 && split[i]) {
+                    for (uint32_t ch = 0; ch < 8u; ++ch) next.push_back(integrateChild(c, ch));
+                    continue;
+                }
+                cells.row(c, level, x[i - b]);
+                if (finals) finals->push_back(c);
+            }
+            integrateBlockTree(x);
+            rows.insert(rows.end(), x[0], x[0] + kIntRow);
+        }
+        integrateReduceRows(rows, T);
+        cur.swap(next);
+        return HPSDF_OK;
+    }
+};
+
+// The call on the calling thread: list 0 of t, the level loop, the struct and the cells
+template <class Cells>
+int hostIntegrateLists(Cells& cells, const ClsTree& t, size_t nNodes, const IntegrateArgs& a, hpsdf_integral* out, hpsdf_integrate_cell** outCells,
+                       uint64_t* outCount) {
+    HostIntegrateLists<Cells> L{cells, a.depth, {}, {}, {}, {}};
+    integrateLeafCells(t.nodes, nNodes, L.cur);
+    IntegrateSums S;
+    if (const int rc = integrateLevels(L, a, (uint32_t)L.cur.size(), outCells != nullptr, S)) return rc;
+    hpsdf_integral r;
+    integrateResult(S, t.rootCentre, t.rootInvSizes, a.samples, &r);
+    return integrateHandOver(S, r, out, outCells, outCount);
+}
+
 // Integrate on the calling thread over the host arrays of t (host_query.cpp)
 int hostIntegrate(const ClsTree& t, size_t nNodes, const IntegrateArgs& a, hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
 

@@ -82,6 +82,11 @@ struct IntegrateCell;  // integrate.hpp
 struct IntegrateArgs;
 int integrateOnDevice(hpsdf_ctx* ctx, const ClsTree& t, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves, const IntegrateArgs& a,
                       hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
+// ---- IntegratePair (integrate_pair.hip): the same for an operation between A and B under a pose; both trees on ctx's device with their
+// cached constants, dLeaves: A's cached list 0, maxDegree: the larger of the two trees'
+struct PairArgs;  // integrate_pair.hpp
+int integratePairOnDevice(hpsdf_ctx* ctx, const ClsTree& tA, const ClsTree& tB, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves,
+                          const PairArgs& p, const IntegrateArgs& a, hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

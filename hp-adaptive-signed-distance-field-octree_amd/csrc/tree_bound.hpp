@@ -204,20 +204,11 @@ struct HostBoundsStack {
 // The centre of the node whose children are being visited is carried in three doubles: going down adds a quarter of the node's size per
 // axis, coming back up takes the same dyadic off again (the child taken at each level is kept in three bits of `path`) -- every centre
 // is a multiple of 2^-12 in [-0.5, 0.5], so both are exact and the centres are the ones classifyBlock keeps in its per-level array.
+// boundsWalk is the map of step 1 followed by boundsWalkRange, the walk from a range [pl, ph] of the root's normalised frame that passed
+// step 1's tests (IntegratePair enters there with a range it clamped itself, integrate_pair.hpp).
 template <class Eval, class Stack>
-__host__ __device__ inline void boundsWalk(const ClsTree& t, const double (&a)[3], const double (&b)[3], uint32_t subdiv, uint32_t maxLeaves,
-                                           const Eval& eval, Stack& st, BoundsRow& R) {
-    R.lo = R.hi = boundsQuietNaN(), R.leaves = 0, R.status = HPSDF_BOUNDS_INVALID;
-    double pl[3], ph[3];
-    bool valid = true;
-    for (int k = 0; k < 3; ++k) {
-        pl[k] = (a[k] - t.rootCentre[k]) * t.rootInvSizes[k];
-        ph[k] = (b[k] - t.rootCentre[k]) * t.rootInvSizes[k];
-        const float fl = (float)pl[k], fh = (float)ph[k];
-        if (!(fl >= -0.5f && fl <= 0.5f && fh >= -0.5f && fh <= 0.5f)) valid = false;  // a corner fails Query's containment test (NaN too)
-        if (!(pl[k] <= ph[k])) valid = false;
-    }
-    if (!valid) return;
+__host__ __device__ inline void boundsWalkRange(const ClsTree& t, const double (&pl)[3], const double (&ph)[3], uint32_t subdiv, uint32_t maxLeaves,
+                                                const Eval& eval, Stack& st, BoundsRow& R) {
     const double inf = boundsInf();
     double lo = inf, hi = -inf;
     uint32_t leaves = 0;
@@ -305,6 +296,23 @@ __host__ __device__ inline void boundsWalk(const ClsTree& t, const double (&a)[3
     }
     if (status != HPSDF_BOUNDS_OK) lo = -inf, hi = inf;
     R.lo = lo, R.hi = hi, R.leaves = leaves, R.status = (uint32_t)status;
+}
+
+template <class Eval, class Stack>
+__host__ __device__ inline void boundsWalk(const ClsTree& t, const double (&a)[3], const double (&b)[3], uint32_t subdiv, uint32_t maxLeaves,
+                                           const Eval& eval, Stack& st, BoundsRow& R) {
+    R.lo = R.hi = boundsQuietNaN(), R.leaves = 0, R.status = HPSDF_BOUNDS_INVALID;
+    double pl[3], ph[3];
+    bool valid = true;
+    for (int k = 0; k < 3; ++k) {
+        pl[k] = (a[k] - t.rootCentre[k]) * t.rootInvSizes[k];
+        ph[k] = (b[k] - t.rootCentre[k]) * t.rootInvSizes[k];
+        const float fl = (float)pl[k], fh = (float)ph[k];
+        if (!(fl >= -0.5f && fl <= 0.5f && fh >= -0.5f && fh <= 0.5f)) valid = false;  // a corner fails Query's containment test (NaN too)
+        if (!(pl[k] <= ph[k])) valid = false;
+    }
+    if (!valid) return;
+    boundsWalkRange(t, pl, ph, subdiv, maxLeaves, eval, st, R);
 }
 
 // n rows on the calling thread (host_query.cpp): the kernels' rows bit for bit.  boxes == nullptr: the cells of *grid.  leaves may be null.

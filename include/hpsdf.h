@@ -884,6 +884,98 @@ HPSDF_API int hpsdf_integrate_host(hpsdf_ctx* ctx, const hpsdf_tree* t, double i
 HPSDF_API int hpsdf_integrate_block(const void* block, size_t size, double iso, uint32_t depth, uint32_t samples, uint32_t max_cells,
                                     hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
 
+/* ---- IntegratePair: guaranteed volume of the CSG of two posed trees (no reference counterpart) ------------------------------------------
+ * Integrate over tree A, with every cell also classified against a second tree B placed under an affine pose: the volume and moments of
+ * the intersection, the union or the difference of the two solids, with no third tree built and no fit error added.
+ *   SA = {x in A's root : Query_A(x) < iso_a}
+ *   SB = {x : Query_B(M x + t) < iso_b}      (Query_B is DBL_MAX outside B's root: such points are not in SB)
+ *   HPSDF_PAIR_INTERSECTION: SA n SB;   HPSDF_PAIR_UNION: (SA u SB) n A's root;   HPSDF_PAIR_DIFFERENCE: SA \ SB
+ * pose[12] is the row-major 3 x 4 matrix [M | t]: a point x of A's world frame is y = M x + t in B's world frame.  M need not be a
+ * rotation; nothing below uses more than |M_jk|.  The region is A's root, the cells are A's cells (hpsdf_integrate_cell, node an index
+ * into A) and every result is in A's frame.  The output is hpsdf_integral with Integrate's meaning: unit_volume_lo <= vol(op) <=
+ * unit_volume_hi is guaranteed (in Integrate's sense), volume, m1 and m2 are estimates; `evaluations` counts evaluations of A's
+ * polynomial as Integrate does (the cells of all lists + q^3 per undecided final cell; work on B is not counted).  For the intersection
+ * volume_hi == 0 proves the solids disjoint inside A's root and volume_lo > 0 proves that they interfere.
+ * Arguments: iso_a, iso_b and the 12 pose entries finite; op <= 2; depth, samples, max_cells as in Integrate; max_leaves in 1..65535.
+ * Host, device and block entries run the same statements (csrc/integrate_pair.hpp; every expression below has its association written,
+ * no multiply-add is fused, -ffp-contract=off) and give the same bits.  The lists, the scan, the cell limit, the reduction, the level
+ * totals and the world transform are Integrate's; only a cell's class and an undecided final cell's samples differ.
+ *   Class of a cell
+ *   1 clsA     Integrate's class of the cell on A with iso_a: one evaluation at the cell's centre.  (Not finite: as Integrate.)
+ *   2 alone    intersection and difference: clsA outside -> outside; union: clsA inside -> inside.  B is not touched.
+ *   3 box      otherwise the cell's image box [a, b] in B's world frame.  With s = 1.0 / (double)(1 << depth), size_k = 1.0 /
+ *              rootInvSizesA_k and per axis k with its integer coordinate i:
+ *                pc = (-0.5 + (double)i * s) + 0.5 * s          (exact)
+ *                cx_k = rootCentreA_k + pc * size_k;   hx_k = (0.5 * s) * size_k
+ *              and per row j of the pose:
+ *                yc_j = ((M_j0 * cx_0 + M_j1 * cx_1) + M_j2 * cx_2) + t_j
+ *                r_j  = (|M_j0| * hx_0 + |M_j1| * hx_1) + |M_j2| * hx_2
+ *                a_j = yc_j - (r_j + delta_j);   b_j = yc_j + (r_j + delta_j)
+ *              with the slack, one value a row for the whole call, computed once on the host,
+ *                X_k = |rootCentreA_k| + 0.5 * size_k
+ *                delta_j = (32 * 2^-53) * (((|M_j0| * X_0 + |M_j1| * X_1) + |M_j2| * X_2) + |t_j|)
+ *   4 clamp    pl_k = (a_k - rootCentreB_k) * rootInvSizesB_k,  ph_k = (b_k - rootCentreB_k) * rootInvSizesB_k: Query's own expression
+ *              (QueryBounds step 1).  PMAX = 0.5 + 2^-25 is the largest double whose (float) cast still passes Query's containment
+ *              test (the cast rounds to nearest, ties to even, and 0.5f is even); PMIN = -PMAX.
+ *                a NaN in pl or ph:                                         clsB undecided, no walk
+ *                else (float)ph_k < -0.5f or (float)pl_k > 0.5f on an axis:   clsB outside, no walk (no point of the box reaches B)
+ *                else if !((float)pl_k >= -0.5f): pl_k = PMIN, partial;      if !((float)ph_k <= 0.5f): ph_k = PMAX, partial
+ *   5 walk     QueryBounds' steps 2 to 4 on B from [pl, ph] with subdiv = 1 and max_leaves: [lo, hi] and a status.
+ *                clsB outside if lo > iso_b;  else inside if hi < iso_b and not partial;  else undecided
+ *              HPSDF_BOUNDS_LEAF_LIMIT has [-inf, inf] and is therefore undecided.  HPSDF_BOUNDS_NOT_FINITE ends the call as a cell of A
+ *              that is not finite does: status HPSDF_INTEGRATE_NOT_FINITE with Integrate's outputs.
+ *   6 combine  operation      outside if                        inside if
+ *              intersection   clsA or clsB is outside           both are inside
+ *              union          both are outside                  clsA or clsB is inside
+ *              difference     clsA is outside or clsB inside    clsA is inside and clsB outside
+ *              everything else is undecided.
+ *   A final undecided cell takes Integrate's q^3 sub-box centres u (in A's leaf) and p (in A's root frame).  At each:
+ *                inA = f_A(u) < iso_a                                                       (Integrate's statements)
+ *                x_k = rootCentreA_k + p_k * size_k;   y_j = ((M_j0 * x_0 + M_j1 * x_1) + M_j2 * x_2) + t_j
+ *                inB = Query_B(y) < iso_b, by the point descent Query uses (DBL_MAX outside B's root and for a NaN)
+ *              and the sub-box's moments are added iff the operation's predicate holds: inA && inB, inA || inB, inA && !inB.  (Where inA
+ *              decides the predicate alone B is not asked; the value is the same.)
+ * Why it holds.  A cell is decided only from statements true of every point of it: clsA is Integrate's; clsB outside means every point
+ * of the image box either fails Query_B's containment test (value DBL_MAX, not < iso_b) or has Query_B > iso_b; clsB inside means
+ * every point of the box passes the test (not partial) and has Query_B < iso_b; the table is the operation's predicate applied to
+ * these.  What is left to show is that the box holds every y the statements above are about:
+ *   the exact image, under the doubles M and t, of the cell's exact box {rootCentreA + p * size : p in the cell} -- the region the
+ *   guarantee speaks of -- and every double y that step 6 computes from a p of the cell.
+ *   Let u = 2^-53 and m_j = sum_k |M_jk| X_k + |t_j|; every point of A's root has |x_k| <= X_k, so m_j bounds the magnitudes that enter
+ *   row j and |yc_j| + r_j <= m_j.  hx_k is exact (a power of two times size_k).  Roundings, each at most u times m_j to first order:
+ *     cx_k (and x_k of step 6): one product and one sum, 2;  a row of M x + t: a product and up to three sums on the longest path, 4
+ *     -- so yc_j is within 6 u m_j of the exact image of the exact centre, and a computed y within 6 u m_j of the exact image of its
+ *     exact point;  r_j: a product and two sums, all positive, at most 3 u r_j too small;  r_j + delta_j: 1;  the last subtraction or
+ *     addition: 1.
+ *   An exact image lies within the exact r_j of the exact centre's image: 6 + 3 + 1 + 1 = 11.  A computed y adds its own 6: 17.  The
+ *   second-order terms are below 17^2 u^2 m_j.  delta_j carries the constant 32: a headroom factor of 32 / 17 over the count.  It is
+ *   derived, not tuned, and at 2^-48 of the scene's size it costs no cell its decision.  delta_j's own roundings (seven, all of positive
+ *   terms) move it by under 2^-50 of itself.
+ *   Steps 4 and 5: pl and ph are monotone in a and b (a subtraction and a multiplication by a positive number), so every y of the box
+ *   has its p within [pl, ph] before the clamp; if (float)ph < -0.5f or (float)pl > 0.5f on an axis the cast of every such p fails the
+ *   test, for the cast is monotone too.  A p the test passes lies in [PMIN, PMAX], so the clamped range still holds every point of the
+ *   box that reaches B, and it passes QueryBounds' step 1: the walk's guarantee applies to it as it stands.
+ *   An overflow in the chain gives an infinite end (clamped: partial) or a NaN (undecided): both only undecide.
+ * Outputs, the cell array and its ownership are Integrate's.  A non-finite pose entry or iso, op > 2, a range outside those above, a
+ * NULL tree, pose or `out`, only one of out_cells and out_n_cells NULL, two trees on different devices: HPSDF_ERR_INVALID_ARGUMENT,
+ * and nothing is written.  tree_a == tree_b is allowed.  hpsdf_integrate_pair_device runs on the context stream (Integrate's launches
+ * per level, with the pair kernels: a lane per cell, B walked with its stack in LDS) and synchronises before it returns; both trees'
+ * constants and A's list 0 are the trees' own caches.  _host computes on the calling thread from the trees' host copies, _block from two
+ * serialised blocks with no device at all; it accepts and refuses blocks as hpsdf_integrate_block does.
+ * Not done: batches of poses in one call; subdiv above 1 on B; rigorous bounds on the moments (Integrate's remark applies); surface
+ * area or contact normals; clipping the region to anything but A's root; a wave cooperating on one walk (a wave costs its slowest
+ * lane, as in QueryBounds). */
+enum { HPSDF_PAIR_INTERSECTION = 0, HPSDF_PAIR_UNION = 1, HPSDF_PAIR_DIFFERENCE = 2 };
+HPSDF_API int hpsdf_integrate_pair_device(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, const hpsdf_tree* tree_b, uint32_t op, const double pose[12],
+                                          double iso_a, double iso_b, uint32_t depth, uint32_t samples, uint32_t max_cells, uint32_t max_leaves,
+                                          hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_integrate_pair_host(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, const hpsdf_tree* tree_b, uint32_t op, const double pose[12],
+                                        double iso_a, double iso_b, uint32_t depth, uint32_t samples, uint32_t max_cells, uint32_t max_leaves,
+                                        hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_integrate_pair_block(const void* block_a, size_t size_a, const void* block_b, size_t size_b, uint32_t op,
+                                         const double pose[12], double iso_a, double iso_b, uint32_t depth, uint32_t samples, uint32_t max_cells,
+                                         uint32_t max_leaves, hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+
 /* ---- Simplify: hp-coarsen a built tree within an RMS bound (no reference counterpart) ---------------------------------------------------
  * Makes a NEW tree from a serialised one: sibling leaves are merged into their parent (h-coarsening) and top degrees are dropped
  * (p-coarsening) wherever that keeps the result within `rms` of the source, cell by cell.  The source block is never written.  No field

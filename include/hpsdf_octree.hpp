@@ -748,6 +748,35 @@ class Octree {
         return r;
     }
 
+    /// The same for an operation between this solid and other_'s under a pose (no reference counterpart; include/hpsdf.h, "IntegratePair"):
+    /// op_ is HPSDF_PAIR_INTERSECTION, _UNION or _DIFFERENCE of {Query < isoA_} with {x : other_.Query(M x + t) < isoB_}, over this
+    /// octree's root and in its frame; pose_ is the row-major 3 x 4 [M | t] (null: the identity).  unit_volume_lo <= vol <= unit_volume_hi
+    /// is guaranteed: for the intersection volume_hi == 0 proves the solids disjoint inside this root, volume_lo > 0 proves they
+    /// interfere.  maxLeaves_ (1..65535) bounds a cell's walk of other_.  Both octrees must live on one device
+    hpsdf_integral IntegratePair(const Octree& other_, uint32_t op_, const double* pose_ = nullptr, f64 isoA_ = 0.0, f64 isoB_ = 0.0,
+                                 uint32_t depth_ = 8, uint32_t samples_ = 2, uint32_t maxCells_ = 1u << 24, uint32_t maxLeaves_ = 256,
+                                 std::vector<hpsdf_integrate_cell>* cells_ = nullptr) const {
+        hpsdf_tree* t = deviceTree();
+        hpsdf_tree* o = other_.deviceTree();
+        if (!t || !o) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        hpsdf_integral r;
+        hpsdf_integrate_cell* cells = nullptr;
+        uint64_t n = 0;
+        check(hpsdf_integrate_pair_device(ctx_, t, o, op_, pose_ ? pose_ : identity, isoA_, isoB_, depth_, samples_, maxCells_, maxLeaves_, &r,
+                                          cells_ ? &cells : nullptr, cells_ ? &n : nullptr));
+        if (cells_) {
+            try {
+                cells_->assign(cells, cells + n);
+            } catch (...) {
+                std::free(cells);
+                throw;
+            }
+            std::free(cells);
+        }
+        return r;
+    }
+
     /// A NEW octree within rms_ of this one, leaf cell by leaf cell, in the root-normalised L2 sense (no reference counterpart;
     /// include/hpsdf.h, "Simplify"): sibling leaves merged into their parent (HPSDF_SIMPLIFY_MERGE) and top degrees dropped
     /// (HPSDF_SIMPLIFY_TRUNCATE) from the coefficients alone -- no field is sampled --, every result cell C with
