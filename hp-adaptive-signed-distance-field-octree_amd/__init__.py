@@ -200,6 +200,12 @@ _SIGNATURES = {
                                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_integrate_pair_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_double, C.c_double, C.c_uint32,
                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_clearance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_clearance_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hpsdf_clearance_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.c_uint32,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_simplify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     "hpsdf_simplify_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     "hpsdf_simplify_transfer": (C.c_int, [C.c_void_p]),
@@ -823,6 +829,13 @@ class DeviceTree:
         return _integrate_pair(lambda *rest: fn(self.ctx.handle, self.handle, other.handle, *rest), op, pose, iso_a, iso_b, depth, samples,
                                max_cells, max_leaves, cells)
 
+    def clearance(self, other, pose=None, iso_a=0.0, depth=10, tol=0.0, max_cells=1 << 24, max_leaves=256, cells=False, host=False):
+        """Clearance (include/hpsdf.h): lo <= min of other's field (B) over {Query_A < iso_a} of this tree (A) under pose <= hi, by
+        branch and bound over A's cells -> Clearance with the witness point that attains hi.  host=True: on the calling thread from
+        the trees' host copies (the same bits)."""
+        fn = lib().hpsdf_clearance_host if host else lib().hpsdf_clearance_device
+        return _clearance(lambda *rest: fn(self.ctx.handle, self.handle, other.handle, *rest), pose, iso_a, depth, tol, max_cells, max_leaves, cells)
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1301,6 +1314,13 @@ class Octree:
             raise HpsdfError(ERR_STATE, "IntegratePair on an empty octree")
         return self._tree.integrate_pair(other._tree, op, pose, iso_a, iso_b, depth, samples, max_cells, max_leaves, cells)
 
+    def Clearance(self, other, pose=None, iso_a=0.0, depth=10, tol=0.0, max_cells=1 << 24, max_leaves=256, cells=False):
+        """The guaranteed minimum of other's field over this solid under a pose (DeviceTree.clearance) -> Clearance: .lo <= it <= .hi,
+        .point (this octree's frame) and .image (other's) where .hi is attained; .gap(iso_b) for two distance fields."""
+        if self._tree is None or other._tree is None:
+            raise HpsdfError(ERR_STATE, "Clearance on an empty octree")
+        return self._tree.clearance(other._tree, pose, iso_a, depth, tol, max_cells, max_leaves, cells)
+
     def Simplify(self, rms, merge=True, truncate=True, stats=False):
         """A NEW Octree on the same context whose field is within `rms` of this one's in the root-normalised L2 sense, leaf cell by leaf
         cell (include/hpsdf.h, "Simplify"): sibling leaves merged into their parent, top degrees dropped, from the coefficients alone.
@@ -1594,6 +1614,57 @@ def integrate_pair_block(block_a, block_b, op, pose=None, iso_a=0.0, iso_b=0.0, 
     a, b = bytes(block_a), bytes(block_b)
     return _integrate_pair(lambda *rest: lib().hpsdf_integrate_pair_block(a, len(a), b, len(b), *rest), op, pose, iso_a, iso_b, depth, samples,
                            max_cells, max_leaves, cells)
+
+
+CLEARANCE_CONVERGED, CLEARANCE_DEPTH, CLEARANCE_CELL_LIMIT, CLEARANCE_EMPTY, CLEARANCE_NOT_FINITE = 0, 1, 2, 3, 4  # HPSDF_CLEARANCE_*
+
+
+class hpsdf_clearance(C.Structure):
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("point", C.c_double * 3), ("image", C.c_double * 3), ("value_a", C.c_double),
+                ("cells_visited", C.c_uint64), ("cells_outside_a", C.c_uint64), ("cells_pruned", C.c_uint64), ("cells_open", C.c_uint64),
+                ("status", C.c_uint32), ("levels", C.c_uint32)]
+
+
+class Clearance:
+    """hpsdf_clearance's fields (arrays as numpy), `raw` (the struct's bytes) and `cells` (the final cells as a CELL_DTYPE array, or
+    None when not asked for).  lo <= min of B's field over A's solid <= hi; hi is B's value at `image`, the image of `point`."""
+
+    def __init__(self, st, cells):
+        self.raw = bytes(st)
+        for name, _ in st._fields_:
+            v = getattr(st, name)
+            setattr(self, name, np.array(v[:]) if hasattr(v, "__len__") else v)
+        self.cells = cells
+
+    def gap(self, iso_b=0.0):
+        """(lo - iso_b, hi - iso_b): for a distance field B the enclosure of the signed clearance of solid A from solid B -- both
+        positive: provably that far apart inside B's root; both negative: A reaches that deep into B."""
+        return self.lo - iso_b, self.hi - iso_b
+
+    def __repr__(self):
+        return "Clearance(status=%d, levels=%d, min in [%r, %r], open cells %d)" % (self.status, self.levels, self.lo, self.hi, self.cells_open)
+
+
+def _clearance(call, pose_, iso_a, depth, tol, max_cells, max_leaves, cells):
+    """call(pose, iso_a, depth, tol, max_cells, max_leaves, out, out_cells, out_n_cells) -> Clearance; the malloc'd cell array copied and freed."""
+    P = pose() if pose_ is None else np.ascontiguousarray(np.asarray(pose_, np.float64).reshape(12))
+    st = hpsdf_clearance()
+    ptr, count = C.c_void_p(), C.c_uint64()
+    check(call(P.ctypes.data_as(C.c_void_p), float(iso_a), _max_iter(depth), float(tol), _max_iter(max_cells), _max_iter(max_leaves), C.byref(st),
+               C.byref(ptr) if cells else None, C.byref(count) if cells else None))
+    arr = None
+    if cells:
+        arr = np.zeros(count.value, CELL_DTYPE)
+        if count.value:
+            C.memmove(arr.ctypes.data, ptr, count.value * CELL_DTYPE.itemsize)
+        lib()._libc.free(ptr)
+    return Clearance(st, arr)
+
+
+def clearance_block(block_a, block_b, pose=None, iso_a=0.0, depth=10, tol=0.0, max_cells=1 << 24, max_leaves=256, cells=False):
+    """hpsdf_clearance_block: DeviceTree.clearance's result from two serialised blocks on the calling thread (no device)."""
+    a, b = bytes(block_a), bytes(block_b)
+    return _clearance(lambda *rest: lib().hpsdf_clearance_block(a, len(a), b, len(b), *rest), pose, iso_a, depth, tol, max_cells, max_leaves, cells)
 
 
 SIMPLIFY_MERGE, SIMPLIFY_TRUNCATE = 1, 2  # HPSDF_SIMPLIFY_*

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "block.hpp"
+#include "clearance.hpp"
 #include "host_call.hpp"
 #include "integrate.hpp"
 #include "integrate_pair.hpp"
@@ -538,6 +539,45 @@ int hpsdf_integrate_pair_host(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_
     const PairArgs p = pairArgs(ctA, op, pose, isoA, isoB, maxLeaves);
     const IntegrateArgs a{isoA, depth, samples, maxCells};
     return hostIntegratePair(ctA, tA->hRecs.size(), ctB, p, a, out, outCells, outCount);
+    HPSDF_CATCH
+}
+
+// Clearance (include/hpsdf.h): the guaranteed minimum of B's field over A's solid under a pose (clearance.hip, clearance.hpp,
+// clearance_host.cpp)
+int hpsdf_clearance_device(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree* tB, const double pose[12], double isoA, uint32_t depth, double tol,
+                           uint32_t maxCells, uint32_t maxLeaves, hpsdf_clearance* out, hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = clearanceArgumentError(pose, isoA, depth, tol, maxCells, maxLeaves, out, outCells, outCount)) return rc;
+    if (!tA || !tB) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (tA->device != tB->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance: the two trees live on different devices");
+    if (const int rc = treeOnContext(ctx, tA)) return rc;
+    if (const int rc = tA->boundConsts(ctx)) return rc;
+    if (const int rc = tB->boundConsts(ctx)) return rc;
+    if (const int rc = tA->integrateLeaves(ctx)) return rc;
+    const ClsTree ctA = clsTreeOnDevice(tA), ctB = clsTreeOnDevice(tB);
+    const PairArgs p = pairArgs(ctA, HPSDF_PAIR_INTERSECTION, pose, isoA, 0.0, maxLeaves);
+    const ClearanceArgs a{depth, maxCells, tol};
+    return clearanceOnDevice(ctx, ctA, ctB, std::max(tA->maxDegree, tB->maxDegree), tA->dLeafCells, tA->nLeafCells, p, a, out, outCells, outCount);
+    HPSDF_CATCH
+}
+
+int hpsdf_clearance_host(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree* tB, const double pose[12], double isoA, uint32_t depth, double tol,
+                         uint32_t maxCells, uint32_t maxLeaves, hpsdf_clearance* out, hpsdf_integrate_cell** outCells, uint64_t* outCount) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (const int rc = clearanceArgumentError(pose, isoA, depth, tol, maxCells, maxLeaves, out, outCells, outCount)) return rc;
+    if (!tA || !tB) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (tA->device != tB->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance: the two trees live on different devices");
+    if (tA->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    for (const hpsdf_tree* t : {tA, tB}) {
+        if (const int hc = t->hostCopies()) return hc;
+        if (const int hc = t->boundHostCopies(ctx)) return hc;
+    }
+    const ClsTree ctA = clsTreeOnHost(tA), ctB = clsTreeOnHost(tB);
+    const PairArgs p = pairArgs(ctA, HPSDF_PAIR_INTERSECTION, pose, isoA, 0.0, maxLeaves);
+    const ClearanceArgs a{depth, maxCells, tol};
+    return hostClearance(ctA, tA->hRecs.size(), ctB, p, a, out, outCells, outCount);
     HPSDF_CATCH
 }
 

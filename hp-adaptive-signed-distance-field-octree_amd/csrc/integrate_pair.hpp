@@ -58,16 +58,21 @@ __host__ __device__ inline void pairImage(const PairArgs& a, const double (&x)[3
     }
 }
 
-// The image box [lo, hi] of cell c in B's world frame (step 3)
-__host__ __device__ inline void pairCellBox(const ClsTree& tA, const PairArgs& a, const IntegrateCell& c, double (&lo)[3], double (&hi)[3]) {
+// The centre cx and the half edges hx of cell c in A's world frame (step 3's first statements; Clearance's witness is cx, clearance.hpp)
+__host__ __device__ inline void pairCellCentre(const ClsTree& tA, const PairArgs& a, const IntegrateCell& c, double (&cx)[3], double (&hx)[3]) {
     const double s = 1.0 / (double)(1u << c.depth);
     const double ijk[3] = {(double)c.i, (double)c.j, (double)c.k};
-    double cx[3], hx[3];
     for (int k = 0; k < 3; ++k) {
         const double pc = (-0.5 + ijk[k] * s) + 0.5 * s;  // exact
         cx[k] = tA.rootCentre[k] + pc * a.sizeA[k];
         hx[k] = (0.5 * s) * a.sizeA[k];
     }
+}
+
+// The image box [lo, hi] of cell c in B's world frame (step 3)
+__host__ __device__ inline void pairCellBox(const ClsTree& tA, const PairArgs& a, const IntegrateCell& c, double (&lo)[3], double (&hi)[3]) {
+    double cx[3], hx[3];
+    pairCellCentre(tA, a, c, cx, hx);
     double yc[3];
     pairImage(a, cx, yc);
     for (int j = 0; j < 3; ++j) {

@@ -87,6 +87,11 @@ int integrateOnDevice(hpsdf_ctx* ctx, const ClsTree& t, int maxDegree, const Int
 struct PairArgs;  // integrate_pair.hpp
 int integratePairOnDevice(hpsdf_ctx* ctx, const ClsTree& tA, const ClsTree& tB, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves,
                           const PairArgs& p, const IntegrateArgs& a, hpsdf_integral* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
+// ---- Clearance (clearance.hip): the minimum of B's field over A's solid under a pose, by branch and bound over A's cells; the trees,
+// dLeaves and maxDegree as for IntegratePair
+struct ClearanceArgs;  // clearance.hpp
+int clearanceOnDevice(hpsdf_ctx* ctx, const ClsTree& tA, const ClsTree& tB, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves,
+                      const PairArgs& p, const ClearanceArgs& a, hpsdf_clearance* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

@@ -976,6 +976,92 @@ HPSDF_API int hpsdf_integrate_pair_block(const void* block_a, size_t size_a, con
                                          const double pose[12], double iso_a, double iso_b, uint32_t depth, uint32_t samples, uint32_t max_cells,
                                          uint32_t max_leaves, hpsdf_integral* out, hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
 
+/* ---- Clearance: guaranteed minimum of one tree's field over another's solid (no reference counterpart) --------------------------------
+ * A branch-and-bound search over tree A's cells for
+ *   m = inf { Query_B(M x + t) : x in A's root, Query_A(x) < iso_a, M x + t passes Query_B's containment test }
+ * (a point whose image leaves B's root has the value DBL_MAX there and never lowers a minimum; m = +inf when no point qualifies).  It
+ * returns an enclosure lo <= m <= hi and a witness point that attains hi.  When B is a distance field m - iso_b is the signed clearance
+ * of solid A from solid B: positive, the solids are provably at least that far apart inside B's root; negative, it is the depth of A's
+ * deepest point inside B and the witness is where that happens.  A tree against itself under the identity gives minus the radius of the
+ * largest inscribed ball and its centre.  Only cells that can still hold the minimiser survive a level, so the work follows the contact
+ * region and not the surface or the volume.  pose[12], the cells (Integrate's: hpsdf_integrate_cell, node an index into A), list 0 and
+ * the child order are IntegratePair's and Integrate's.
+ * Arguments: iso_a and the 12 pose entries finite; depth D in 0..15; tol finite and >= 0; max_cells in 8..2^28; max_leaves in 1..65535.
+ * Host, device and block entries run the same statements (csrc/clearance.hpp; every association written, -ffp-contract=off) and give
+ * the same bits.
+ *   The rule.  best = +inf with no witness; finals is empty.  For each list l (the cells of relative level l, pos a cell's position in
+ *   the list) three steps run in order:
+ *   1 bound    clsA = Integrate's class of the cell on A with iso_a.  A cell that is not finite ends the call: status
+ *              HPSDF_CLEARANCE_NOT_FINITE, lo = -inf, hi = +inf, point, image and value_a quiet NaNs, every counter 0, no cells.
+ *              clsA outside: the cell is dropped and counted in cells_outside_a.  Otherwise IntegratePair's steps 3 and 4 (the image
+ *              box with its slack delta, the clamp to B's root):
+ *                no point of the box reaches B:  blo = +inf          a NaN:  blo = -inf
+ *                else QueryBounds' walk of B over the clamped range with subdiv = 1 and max_leaves: blo = its lo (HPSDF_BOUNDS_LEAF_LIMIT
+ *                gives -inf; HPSDF_BOUNDS_NOT_FINITE ends the call as above).
+ *              Whether the box is partly outside B's root does not matter: such points cannot lower a minimum.
+ *   2 witness  for every cell that was walked: x = cx, the cell's centre in A's world frame as IntegratePair's step 3 computes it;
+ *              va = Query_A(x) by Query's point descent; if va < iso_a: y_j = ((M_j0 * x_0 + M_j1 * x_1) + M_j2 * x_2) + t_j and
+ *              vb = Query_B(y); the cell is a candidate iff vb < DBL_MAX.  The level's candidate is the lexicographic minimum of
+ *              (vb, pos) -- it does not depend on the order of evaluation -- and replaces best iff vb < best, strictly.
+ *   3 prune    with the updated best a cell survives iff blo <= best and blo < +inf (a cell with blo = +inf holds no point with a value
+ *              in B); the rest are counted in cells_pruned.  A survivor at absolute depth D is final and joins finals with its blo, a
+ *              survivor above D is a split candidate.  L = min(blo of finals, blo of the split candidates).
+ *              no finals and no split candidates:   status HPSDF_CLEARANCE_EMPTY, lo = hi = +inf, no witness, stop
+ *              best - L <= tol:                     status HPSDF_CLEARANCE_CONVERGED, the split candidates join finals, stop
+ *              8 * candidates > max_cells:          status HPSDF_CLEARANCE_CELL_LIMIT, the same, stop
+ *              no split candidates:                 status HPSDF_CLEARANCE_DEPTH, stop
+ *              otherwise the split candidates' eight children each, in list order, form list l + 1.
+ *              A level's new finals follow the earlier ones in list order.
+ *   At the end hi = best, lo = the minimum of blo over finals; finals with blo > hi are removed, their order kept, and counted in
+ *   cells_pruned; out_cells holds what is left with cls = clsA, cells_open is their number.  With no witness hi = +inf and point, image
+ *   and value_a are quiet NaNs.  Otherwise point = x of the witness, image = y, value_a = va and Query_B(image) == hi, bit for bit.
+ *   cells_visited is the sum of the list lengths, levels the index of the last list.
+ * Why it holds.  blo bounds Query_B at every y of the cell's image box that reaches B -- IntegratePair's argument with the same delta --
+ * and the box holds the computed image of the cell's centre, so blo <= vb for a candidate.  hi is a value Query_B takes at the image of
+ * a point of A's root with Query_A < iso_a: hi >= m.  A cell dropped by A's class holds no point with Query_A < iso_a (Integrate's
+ * argument); a pruned cell has every value above a best that is >= m, or no value at all.  A point x with Query_A(x) < iso_a and a value
+ * v = Query_B(M x + t) lies at every level in a cell with blo <= v < +inf; while v <= best that cell survives, so every point whose
+ * value is at most the final hi -- the minimiser among them -- lies in a final cell, and lo <= m.  (The cell of the final witness is one
+ * of them: blo <= vb = best.)  tol only stops the loop and is no part of the guarantee; the statuses CELL_LIMIT and DEPTH only leave a
+ * wider enclosure.  lo is a statement about all x with Query_A(x) < iso_a: it is true even if that set is empty (then hi = +inf).
+ * A non-finite pose entry, iso_a or tol, tol < 0, a range outside those above, a NULL tree, pose or `out`, only one of out_cells and
+ * out_n_cells NULL, two trees on different devices: HPSDF_ERR_INVALID_ARGUMENT, and nothing is written.  tree_a == tree_b is allowed.
+ * The cell array and its ownership are Integrate's.  hpsdf_clearance_device runs on the context stream -- per level a bound kernel (a
+ * lane per cell, B walked with its stack in LDS, the (vb, pos) minimum reduced per workgroup in LDS, shuffles and DPP), a fold that
+ * updates best in device memory, a prune kernel, a rocPRIM scan, one read-back and an emit kernel -- and synchronises before it returns;
+ * no atomic decides a value.  _host computes on the calling thread from the trees' host copies, _block from two serialised blocks with
+ * no device at all.
+ * Not done: maximisation; batches of poses in one call; subdiv above 1 on B; upper bounds without a witness (an inside cell's walk
+ * gives a hi that no sample attains); best-first ordering of the cells; contact normals (call QueryGradient of B at `image`). */
+enum {
+    HPSDF_CLEARANCE_CONVERGED = 0,
+    HPSDF_CLEARANCE_DEPTH = 1,
+    HPSDF_CLEARANCE_CELL_LIMIT = 2,
+    HPSDF_CLEARANCE_EMPTY = 3,
+    HPSDF_CLEARANCE_NOT_FINITE = 4
+};
+typedef struct hpsdf_clearance { /* 112 bytes */
+    double lo, hi;            /* lo <= m <= hi */
+    double point[3];          /* the witness in A's world frame */
+    double image[3];          /* M point + t: Query_B there is hi */
+    double value_a;           /* Query_A(point) < iso_a */
+    uint64_t cells_visited;   /* the sum of the list lengths */
+    uint64_t cells_outside_a; /* dropped by A's class */
+    uint64_t cells_pruned;    /* dropped by their bound */
+    uint64_t cells_open;      /* the final cells left: *out_n_cells */
+    uint32_t status;          /* HPSDF_CLEARANCE_* */
+    uint32_t levels;
+} hpsdf_clearance;
+HPSDF_API int hpsdf_clearance_device(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, const hpsdf_tree* tree_b, const double pose[12], double iso_a,
+                                     uint32_t depth, double tol, uint32_t max_cells, uint32_t max_leaves, hpsdf_clearance* out,
+                                     hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_clearance_host(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, const hpsdf_tree* tree_b, const double pose[12], double iso_a,
+                                   uint32_t depth, double tol, uint32_t max_cells, uint32_t max_leaves, hpsdf_clearance* out,
+                                   hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_clearance_block(const void* block_a, size_t size_a, const void* block_b, size_t size_b, const double pose[12], double iso_a,
+                                    uint32_t depth, double tol, uint32_t max_cells, uint32_t max_leaves, hpsdf_clearance* out,
+                                    hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+
 /* ---- Simplify: hp-coarsen a built tree within an RMS bound (no reference counterpart) ---------------------------------------------------
  * Makes a NEW tree from a serialised one: sibling leaves are merged into their parent (h-coarsening) and top degrees are dropped
  * (p-coarsening) wherever that keeps the result within `rms` of the source, cell by cell.  The source block is never written.  No field

@@ -777,6 +777,33 @@ class Octree {
         return r;
     }
 
+    /// The guaranteed minimum of other_'s field over this solid {Query < isoA_} under a pose (no reference counterpart; include/hpsdf.h,
+    /// "Clearance"): lo <= min <= hi by branch and bound over this octree's cells down to depth_, stopping once hi - lo <= tol_; point
+    /// (this octree's frame) and image (other_'s) are where hi is attained.  For two distance fields lo - isoB > 0 proves the solids that
+    /// far apart inside other_'s root, hi - isoB < 0 that this solid reaches that deep into other_'s.  pose_ as in IntegratePair
+    hpsdf_clearance Clearance(const Octree& other_, const double* pose_ = nullptr, f64 isoA_ = 0.0, uint32_t depth_ = 10, f64 tol_ = 0.0,
+                              uint32_t maxCells_ = 1u << 24, uint32_t maxLeaves_ = 256, std::vector<hpsdf_integrate_cell>* cells_ = nullptr) const {
+        hpsdf_tree* t = deviceTree();
+        hpsdf_tree* o = other_.deviceTree();
+        if (!t || !o) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        hpsdf_clearance r;
+        hpsdf_integrate_cell* cells = nullptr;
+        uint64_t n = 0;
+        check(hpsdf_clearance_device(ctx_, t, o, pose_ ? pose_ : identity, isoA_, depth_, tol_, maxCells_, maxLeaves_, &r, cells_ ? &cells : nullptr,
+                                     cells_ ? &n : nullptr));
+        if (cells_) {
+            try {
+                cells_->assign(cells, cells + n);
+            } catch (...) {
+                std::free(cells);
+                throw;
+            }
+            std::free(cells);
+        }
+        return r;
+    }
+
     /// A NEW octree within rms_ of this one, leaf cell by leaf cell, in the root-normalised L2 sense (no reference counterpart;
     /// include/hpsdf.h, "Simplify"): sibling leaves merged into their parent (HPSDF_SIMPLIFY_MERGE) and top degrees dropped
     /// (HPSDF_SIMPLIFY_TRUNCATE) from the coefficients alone -- no field is sampled --, every result cell C with
