@@ -145,6 +145,7 @@ _SIGNATURES = {
     "hpsdf_field_eval_wave_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hpsdf_field_eval_lane_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hpsdf_selftest_acosf": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p]),
+    "hpsdf_selftest_running_total": (C.c_int, [C.c_void_p, C.c_double, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_tree_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "hpsdf_tree_destroy": (C.c_int, [C.c_void_p]),
     "hpsdf_tree_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -1136,6 +1137,26 @@ def selftest_acosf(ctx, first_bits, stride, n):
     out = np.empty(n, np.float32)
     check(lib().hpsdf_selftest_acosf(ctx.handle, first_bits, stride, n, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+CHAIN_OPS, CHAIN_ROUND0 = 0, 1
+CHAIN_ALL_WAVES, CHAIN_THIRTEEN_WAVES = 0, 1
+
+
+def selftest_running_total(ctx, total0, ops=None, errs=None, batch_err=None, population=CHAIN_ALL_WAVES):
+    """Create's running total on chosen operands, by the device code Create runs: total0 + x[0] + x[1] + ... in order, as a float64.
+    x = ops, or -- errs and batch_err given -- errs[9 k] - batch_err[k], formed on the device as round 0 forms it."""
+    out = np.empty(1, np.float64)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    if ops is not None:
+        ops = np.ascontiguousarray(ops, np.float64)
+        check(lib().hpsdf_selftest_running_total(ctx.handle, total0, ops.size, CHAIN_OPS, population, ptr(ops), None, None, ptr(out)))
+    else:
+        errs, batch_err = np.ascontiguousarray(errs, np.float64), np.ascontiguousarray(batch_err, np.float64)
+        if errs.size != 9 * batch_err.size:
+            raise ValueError("errs holds nine doubles a job")
+        check(lib().hpsdf_selftest_running_total(ctx.handle, total0, batch_err.size, CHAIN_ROUND0, population, None, ptr(errs), ptr(batch_err), ptr(out)))
+    return out[0]
 
 
 def bench_fit(ctx, config, field, degree, depth, n_cells, repeats=5):

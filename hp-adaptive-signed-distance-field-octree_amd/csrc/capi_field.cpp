@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "frontier_dev.hpp"
 #include "host_call.hpp"
 #include "launch.hpp"
 #include "runtime.hpp"
@@ -390,6 +391,29 @@ int hpsdf_selftest_acosf(hpsdf_ctx* ctx, uint32_t first_bits, uint32_t stride, s
     const auto dOut = arr.out(out, n);
     return hostCall(ctx, arr, [&] {
         HPSDF_HIP(launchAcosfSelftest(ctx->stream, first_bits, stride, n, dOut));
+        return (int)HPSDF_OK;
+    });
+    HPSDF_CATCH
+}
+
+int hpsdf_selftest_running_total(hpsdf_ctx* ctx, double total0, size_t n, int source, int population, const double* ops, const double* errs,
+                                 const double* batch_err, double* out) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    const bool round0 = source == HPSDF_CHAIN_ROUND0;
+    if (source != HPSDF_CHAIN_OPS && !round0) return fail(HPSDF_ERR_INVALID_ARGUMENT, "unknown source");
+    if (population != HPSDF_CHAIN_ALL_WAVES && population != HPSDF_CHAIN_THIRTEEN_WAVES) return fail(HPSDF_ERR_INVALID_ARGUMENT, "unknown population");
+    if (n >= ((size_t)1 << 24)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "n must be below 2^24");
+    if (!out || (n && (round0 ? !errs || !batch_err : !ops))) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    // (the call's own arrays in the context's host-call scratch: the frontier workspace of Create is not touched)
+    HostArrays arr;
+    const auto dOps = arr.in(round0 ? nullptr : ops, round0 ? 0 : n);  // (an array the source does not read: no copy)
+    const auto dErrs = arr.in(round0 ? errs : nullptr, round0 ? 9 * n : 0);
+    const auto dBatchErr = arr.in(round0 ? batch_err : nullptr, round0 ? n : 0);
+    const auto dOut = arr.out(out, 1);
+    const HostArrays::Dev<FrHdr> dHdr{arr.add(nullptr, nullptr, sizeof(FrHdr))};  // (scratch: neither copied in nor out)
+    return hostCall(ctx, arr, [&] {
+        HPSDF_HIP(frLaunchRunningTotal(ctx->stream, dHdr, dOps, dErrs, dBatchErr, total0, (uint32_t)n, round0, population == HPSDF_CHAIN_ALL_WAVES, dOut));
         return (int)HPSDF_OK;
     });
     HPSDF_CATCH

@@ -1193,7 +1193,9 @@ __device__ double frRunChain(const FrDev& d, FrLds& L, double total, uint32_t nO
             // a fused multiply-add -- i.e. D = (((C + a0) + a1) + a2) + a3 with IEEE rounding after every step, the very additions of
             // Octree.cpp:253-290 in the reference's order (tools/mfma_chain_lab.hip: 262 144 random sums of mixed magnitudes and signs,
             // signed zeros, subnormals and half-ulp ties bit for bit equal to the sequential v_add_f64 sum -- and unequal to the reversed
-            // and to the exactly rounded sum).  A dependent chain of them costs 20.6 cycles an instruction = 5.2 cycles an addition
+            // and to the exactly rounded sum; the standing evidence is tests/test_gpu_running_total.py, which runs THIS function through
+            // hpsdf_selftest_running_total on such operands at every border of the remainder, the step tail, the batches and the chunks,
+            // from both operand sources and with both wave populations, and asks for the sequential sum's bits).  A dependent chain of them costs 20.6 cycles an instruction = 5.2 cycles an addition
             // against v_add_f64's 8.7 (rounds 2-5: 9.3 with its operands fed from LDS).  Output (0, 0) of block 0 -- lane 0 -- sums
             // the A operands of lanes 0, 16, 32, 48 in that order, so lane l supplies operand 4 t + (l >> 4) of step t; the other
             // fifteen outputs of every block compute sums nobody reads.  Sixteen steps' operands are in registers while the next
@@ -1454,6 +1456,17 @@ __global__ __launch_bounds__(1024) void fr_round_kernel(FrDev d, int flags) {
         frChainTotal(d, L, chain0);
     else
         frUpdateJobs(d, L);
+}
+
+// Diagnostics (hpsdf_selftest_running_total): frRunChain itself on operands the caller chose, as one workgroup of fr_round_kernel's shape
+// calls it -- `allWaves`: all sixteen waves (frLeadRound), else waves 4, 8 and 12 have left before (frChainTotal).  d holds what
+// frRunChain reads and nothing else: hdr (a header's worth of memory nobody reads: one rank, no stamps), ops or errs and batchErr.
+__global__ __launch_bounds__(1024) void fr_running_total_kernel(FrDev d, double total0, uint32_t n, int round0, int allWaves, double* out) {
+    __shared__ FrLds L;
+    const uint32_t wave = threadIdx.x >> 6;
+    if (!allWaves && wave != 0 && (wave & 3u) == 0) return;  // (whole waves, as in frChainTotal)
+    const double total = frRunChain(d, L, total0, n, round0 != 0);
+    if (threadIdx.x == 0) *out = total;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1763,6 +1776,14 @@ hipError_t frLaunchTasks(hipStream_t stream, const FrDev& d, uint32_t jobs) {  /
 }
 hipError_t frLaunchRound(hipStream_t stream, const FrDev& d, uint32_t jobs, int flags) {  // workgroup 0 and the running total's, 128 jobs each in between
     hipLaunchKernelGGL(fr_round_kernel, dim3(2 + (jobs + 127u) / 128u), dim3(1024), 0, stream, d, flags);
+    return hipGetLastError();
+}
+hipError_t frLaunchRunningTotal(hipStream_t stream, FrHdr* hdr, const double* ops, const double* errs, const double* batchErr, double total0,
+                                uint32_t n, bool round0, bool allWaves, double* out) {  // one workgroup
+    FrDev d{};  // (stamps = 0)
+    d.hdr = hdr, d.world = 1;
+    d.ops = const_cast<double*>(ops), d.errs = const_cast<double*>(errs), d.batchErr = batchErr;
+    hipLaunchKernelGGL(fr_running_total_kernel, dim3(1), dim3(1024), 0, stream, d, total0, n, round0 ? 1 : 0, allWaves ? 1 : 0, out);
     return hipGetLastError();
 }
 hipError_t frLaunchSubtree(hipStream_t stream, const FrDev& d, uint32_t nodes) {  // a node a lane

@@ -196,6 +196,9 @@ hipError_t frLaunchEmit(hipStream_t stream, const FrDev& d, uint32_t jobs);
 hipError_t frLaunchBatch(hipStream_t stream, const FrDev& d);
 hipError_t frLaunchTasks(hipStream_t stream, const FrDev& d, uint32_t jobs);
 hipError_t frLaunchRound(hipStream_t stream, const FrDev& d, uint32_t jobs, int flags);  // jobs of the round being closed
+// (diagnostics: the running total's chain alone, on the caller's operands -- ops[n], or errs[9 n] and batchErr[n] when round0; hdr: sizeof(FrHdr) bytes)
+hipError_t frLaunchRunningTotal(hipStream_t stream, FrHdr* hdr, const double* ops, const double* errs, const double* batchErr, double total0,
+                                uint32_t n, bool round0, bool allWaves, double* out);
 hipError_t frLaunchSubtree(hipStream_t stream, const FrDev& d, uint32_t nodes);
 hipError_t frLaunchStore(hipStream_t stream, const FrDev& d, uint32_t nodes);
 hipError_t frLaunchPackPos(hipStream_t stream, const FrDev& d);

@@ -276,6 +276,18 @@ HPSDF_API int hpsdf_field_eval_lane_host(hpsdf_ctx* ctx, const hpsdf_field* f, c
  * glibc >= 2.41 (correctly rounded CORE-MATH acosf), musl and other libms may differ from it in the last place; the tests
  * detect that (tests/test_product_cpu.py compares with the machine's libm and says which one it found). */
 HPSDF_API int hpsdf_selftest_acosf(hpsdf_ctx* ctx, uint32_t first_bits, uint32_t stride, size_t n, float* out);
+/* Diagnostics: the running total of Create's stop rule (Octree.cpp:253-290) on operands of the caller's choice -- the device code
+ * Create itself runs (one workgroup; four additions an instruction on the matrix pipe), not a copy of it.  *out = total0 + x[0] + x[1]
+ * + ... + x[n - 1], one IEEE double addition after the other in that order: bit for bit what a sequential loop on the host gives
+ * (tests/test_gpu_running_total.py holds it to that).  source HPSDF_CHAIN_OPS: x = ops[0 .. n) (rounds >= 1); HPSDF_CHAIN_ROUND0:
+ * x[k] = errs[9 k] - batch_err[k], formed on the device as round 0 does (errs holds 9 n doubles, batch_err n); the arrays of the
+ * other source are not read and may be NULL.  population: all sixteen waves of the workgroup take part, as where round 0's total is added
+ * up, or thirteen (waves 4, 8 and 12 have left), as in later rounds.  n = 0 gives total0; n >= 2^24, an unknown source or population, a
+ * NULL out or a NULL array the source reads with n > 0: HPSDF_ERR_INVALID_ARGUMENT, *out untouched.  Leaves Create's state alone. */
+enum { HPSDF_CHAIN_OPS = 0, HPSDF_CHAIN_ROUND0 = 1 };
+enum { HPSDF_CHAIN_ALL_WAVES = 0, HPSDF_CHAIN_THIRTEEN_WAVES = 1 };
+HPSDF_API int hpsdf_selftest_running_total(hpsdf_ctx* ctx, double total0, size_t n, int source, int population, const double* ops,
+                                           const double* errs, const double* batch_err, double* out);
 /* Diagnostics (no reference counterpart; HPSDF_ERR_UNSUPPORTED unless the library was built with
  * -DHPSDF_MESH_STATS_BUILD): BVH traversal counters of a mesh field created while the environment
  * variable HPSDF_MESH_STATS was set -- out[0] wave-wide closest-triangle queries (64 points each), [1] BVH nodes they visited,
