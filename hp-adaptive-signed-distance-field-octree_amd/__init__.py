@@ -207,7 +207,13 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "hpsdf_clearance_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "hpsdf_simplify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
+    "hpsdf_clearance_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_double,
+                                               C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "hpsdf_clearance_batch_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_double,
+                                             C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "hpsdf_clearance_batch_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32,
+                                              C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "hpsdf_simplify":(C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     "hpsdf_simplify_block": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]),
     "hpsdf_simplify_transfer": (C.c_int, [C.c_void_p]),
     "hpsdf_query_ray_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -837,6 +843,16 @@ class DeviceTree:
         fn = lib().hpsdf_clearance_host if host else lib().hpsdf_clearance_device
         return _clearance(lambda *rest: fn(self.ctx.handle, self.handle, other.handle, *rest), pose, iso_a, depth, tol, max_cells, max_leaves, cells)
 
+    def clearance_batch(self, other, poses, iso_a=0.0, depth=10, tol=0.0, max_cells=1 << 24, max_leaves=256, decide=None, max_total_cells=1 << 24,
+                        host=False):
+        """clearance for n poses ([n, 12], or a sequence of pose(...)) in one device call (include/hpsdf.h, "Clearance", "Batches") ->
+        ClearanceBatch; element i is clearance(other, poses[i], ...)'s struct, byte for byte.  decide: a pose stops with
+        CLEARANCE_DECIDED once lo > decide or hi < decide is proven (None: off); max_total_cells: the cells of all poses' lists of one
+        pass together.  host=True: a loop on the calling thread from the trees' host copies."""
+        fn = lib().hpsdf_clearance_batch_host if host else lib().hpsdf_clearance_batch_device
+        return _clearance_batch(lambda *rest: fn(self.ctx.handle, self.handle, other.handle, *rest), poses, iso_a, depth, tol, max_cells, max_leaves,
+                                decide, max_total_cells)
+
     def query_ray(self, origins, directions, t_max, t_init=None):
         """Octree::QueryRay per row -> (hit u8 [n], t f64 [n]); t rows of misses keep t_init."""
         o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
@@ -1342,6 +1358,12 @@ class Octree:
             raise HpsdfError(ERR_STATE, "Clearance on an empty octree")
         return self._tree.clearance(other._tree, pose, iso_a, depth, tol, max_cells, max_leaves, cells)
 
+    def ClearanceBatch(self, other, poses, iso_a=0.0, depth=10, tol=0.0, max_cells=1 << 24, max_leaves=256, decide=None, max_total_cells=1 << 24):
+        """Clearance for n poses in one device call (DeviceTree.clearance_batch) -> ClearanceBatch"""
+        if self._tree is None or other._tree is None:
+            raise HpsdfError(ERR_STATE, "ClearanceBatch on an empty octree")
+        return self._tree.clearance_batch(other._tree, poses, iso_a, depth, tol, max_cells, max_leaves, decide, max_total_cells)
+
     def Simplify(self, rms, merge=True, truncate=True, stats=False):
         """A NEW Octree on the same context whose field is within `rms` of this one's in the root-normalised L2 sense, leaf cell by leaf
         cell (include/hpsdf.h, "Simplify"): sibling leaves merged into their parent, top degrees dropped, from the coefficients alone.
@@ -1686,6 +1708,55 @@ def clearance_block(block_a, block_b, pose=None, iso_a=0.0, depth=10, tol=0.0, m
     """hpsdf_clearance_block: DeviceTree.clearance's result from two serialised blocks on the calling thread (no device)."""
     a, b = bytes(block_a), bytes(block_b)
     return _clearance(lambda *rest: lib().hpsdf_clearance_block(a, len(a), b, len(b), *rest), pose, iso_a, depth, tol, max_cells, max_leaves, cells)
+
+
+CLEARANCE_DECIDED = 5  # HPSDF_CLEARANCE_DECIDED: the batch entries' `decide` only
+CLEARANCE_DTYPE = np.dtype([("lo", "<f8"), ("hi", "<f8"), ("point", "<f8", (3,)), ("image", "<f8", (3,)), ("value_a", "<f8"),
+                            ("cells_visited", "<u8"), ("cells_outside_a", "<u8"), ("cells_pruned", "<u8"), ("cells_open", "<u8"),
+                            ("status", "<u4"), ("levels", "<u4")])
+assert CLEARANCE_DTYPE.itemsize == C.sizeof(hpsdf_clearance) == 112
+
+
+class ClearanceBatch:
+    """n hpsdf_clearance structs of one batch call: `array` (a CLEARANCE_DTYPE array; every field is also an attribute, an array over
+    the poses), `raw` (the n x 112 bytes); len() and [i] -> the Clearance of pose i (no cells: batches return none)."""
+
+    def __init__(self, array):
+        self.array = array
+        self.raw = array.tobytes()
+        for name in CLEARANCE_DTYPE.names:
+            setattr(self, name, array[name])
+
+    def __len__(self):
+        return len(self.array)
+
+    def __getitem__(self, i):
+        return Clearance(hpsdf_clearance.from_buffer_copy(self.array[i].tobytes()), None)
+
+    def gap(self, iso_b=0.0):
+        """(lo - iso_b, hi - iso_b) for every pose: Clearance.gap, as two arrays"""
+        return self.lo - iso_b, self.hi - iso_b
+
+    def __repr__(self):
+        return "ClearanceBatch(%d poses, statuses %s)" % (len(self), sorted(set(self.status.tolist())))
+
+
+def _clearance_batch(call, poses, iso_a, depth, tol, max_cells, max_leaves, decide, max_total_cells):
+    """call(poses, n, iso_a, depth, tol, decide, max_cells, max_leaves, max_total_cells, out) -> ClearanceBatch; poses: [n, 12] or a
+    sequence of pose(...)"""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12))
+    out = np.zeros(len(P), CLEARANCE_DTYPE)
+    check(call(P.ctypes.data_as(C.c_void_p), len(P), float(iso_a), _max_iter(depth), float(tol), float("nan") if decide is None else float(decide),
+               _max_iter(max_cells), _max_iter(max_leaves), _max_iter(max_total_cells), out.ctypes.data_as(C.c_void_p)))
+    return ClearanceBatch(out)
+
+
+def clearance_batch_block(block_a, block_b, poses, iso_a=0.0, depth=10, tol=0.0, max_cells=1 << 24, max_leaves=256, decide=None,
+                          max_total_cells=1 << 24):
+    """hpsdf_clearance_batch_block: DeviceTree.clearance_batch's result from two serialised blocks on the calling thread (no device)."""
+    a, b = bytes(block_a), bytes(block_b)
+    return _clearance_batch(lambda *rest: lib().hpsdf_clearance_batch_block(a, len(a), b, len(b), *rest), poses, iso_a, depth, tol, max_cells,
+                            max_leaves, decide, max_total_cells)
 
 
 SIMPLIFY_MERGE, SIMPLIFY_TRUNCATE = 1, 2  # HPSDF_SIMPLIFY_*

@@ -17,7 +17,7 @@ HOOK_SOURCES = ["frontier_build.cpp", "capi_build.cpp"]
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
 
 # (the three fit_<kind>.hip are the longest compiles -- they go first)
-SOURCES = ["fit_mesh.hip", "fit_analytic.hip", "fit_samples.hip", "fit.hip", "kernels.hip", "mesh_field.hip", "frontier.hip", "fit_mfma.hip", "fit_low.hip", "mesh_build.hip", "cg.hip", "continuity_asm.hip", "surface.hip", "surface_sparse.hip", "surface_dual.hip", "query_gradient.hip", "query_hessian.hip", "project.hip", "cast_rays.hip", "query_bounds.hip", "integrate.hip", "integrate_pair.hip", "clearance.hip", "simplify.hip", "tables.cpp", "builder.cpp", "mesh.cpp", "obj.cpp", "continuity.cpp", "host_query.cpp", "integrate_pair_host.cpp", "clearance_host.cpp", "simplify_host.cpp", "frontier_build.cpp", "runtime.cpp", "capi_field.cpp", "capi_tree.cpp", "capi_build.cpp", "bench_fit.cpp"]
+SOURCES = ["fit_mesh.hip", "fit_analytic.hip", "fit_samples.hip", "fit.hip", "kernels.hip", "mesh_field.hip", "frontier.hip", "fit_mfma.hip", "fit_low.hip", "mesh_build.hip", "cg.hip", "continuity_asm.hip", "surface.hip", "surface_sparse.hip", "surface_dual.hip", "query_gradient.hip", "query_hessian.hip", "project.hip", "cast_rays.hip", "query_bounds.hip", "integrate.hip", "integrate_pair.hip", "clearance.hip", "clearance_batch.hip", "simplify.hip", "tables.cpp", "builder.cpp", "mesh.cpp", "obj.cpp", "continuity.cpp", "host_query.cpp", "integrate_pair_host.cpp", "clearance_host.cpp", "simplify_host.cpp", "frontier_build.cpp", "runtime.cpp", "capi_field.cpp", "capi_tree.cpp", "capi_build.cpp", "bench_fit.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))  # every header: an edit to any of them rebuilds every object
 # what a variant build compiles again: the units that hold the code its flags change
 QUERY_SOURCES = ("kernels.hip",)  # the Query kernels (-DHPSDF_QUERY_LAB_BUILD)

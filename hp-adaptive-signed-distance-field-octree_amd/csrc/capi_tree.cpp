@@ -581,6 +581,44 @@ int hpsdf_clearance_host(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree*
     HPSDF_CATCH
 }
 
+// ClearanceBatch (include/hpsdf.h, "Clearance", "Batches"): Clearance for n poses in one call (clearance_batch.hip; the host entry is a
+// loop of hostClearance)
+int hpsdf_clearance_batch_device(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree* tB, const double* poses, size_t n, double isoA, uint32_t depth,
+                                 double tol, double decide, uint32_t maxCells, uint32_t maxLeaves, uint32_t maxTotalCells, hpsdf_clearance* out) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (n == 0) return HPSDF_OK;
+    if (const int rc = clearanceBatchArgumentError(poses, n, isoA, depth, tol, decide, maxCells, maxLeaves, maxTotalCells, out)) return rc;
+    if (!tA || !tB) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (tA->device != tB->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance_batch: the two trees live on different devices");
+    if (const int rc = treeOnContext(ctx, tA)) return rc;
+    if (const int rc = tA->boundConsts(ctx)) return rc;
+    if (const int rc = tB->boundConsts(ctx)) return rc;
+    if (const int rc = tA->integrateLeaves(ctx)) return rc;
+    const ClearanceArgs a{depth, maxCells, tol, decide};
+    return clearanceBatchOnDevice(ctx, clsTreeOnDevice(tA), clsTreeOnDevice(tB), std::max(tA->maxDegree, tB->maxDegree), tA->dLeafCells, tA->nLeafCells,
+                                  poses, n, isoA, maxLeaves, a, maxTotalCells, out);
+    HPSDF_CATCH
+}
+
+int hpsdf_clearance_batch_host(hpsdf_ctx* ctx, const hpsdf_tree* tA, const hpsdf_tree* tB, const double* poses, size_t n, double isoA, uint32_t depth,
+                               double tol, double decide, uint32_t maxCells, uint32_t maxLeaves, uint32_t maxTotalCells, hpsdf_clearance* out) {
+    HPSDF_TRY
+    if (!ctx) return fail(HPSDF_ERR_NO_DEVICE, "a device context is required");
+    if (n == 0) return HPSDF_OK;
+    if (const int rc = clearanceBatchArgumentError(poses, n, isoA, depth, tol, decide, maxCells, maxLeaves, maxTotalCells, out)) return rc;
+    if (!tA || !tB) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null tree");
+    if (tA->device != tB->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance_batch: the two trees live on different devices");
+    if (tA->device != ctx->device) return fail(HPSDF_ERR_INVALID_ARGUMENT, "tree lives on another device");
+    for (const hpsdf_tree* t : {tA, tB}) {
+        if (const int hc = t->hostCopies()) return hc;
+        if (const int hc = t->boundHostCopies(ctx)) return hc;
+    }
+    const ClearanceArgs a{depth, maxCells, tol, decide};
+    return hostClearanceBatch(clsTreeOnHost(tA), tA->hRecs.size(), clsTreeOnHost(tB), poses, n, isoA, maxLeaves, a, out);
+    HPSDF_CATCH
+}
+
 // Simplify (include/hpsdf.h): a coarser tree from a serialised one, within an RMS bound (simplify.hip, simplify.hpp; the device-free
 // entry is simplify_host.cpp's)
 int hpsdf_simplify(hpsdf_ctx* ctx, const void* block, size_t size, double rms, uint32_t flags, void** out_block, size_t* out_size,

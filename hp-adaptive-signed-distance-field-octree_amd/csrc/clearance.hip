@@ -26,6 +26,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "clearance.hpp"
+#include "clearance_dev.hpp"
 #include "dev_pool.hpp"
 #include "device_types.hpp"
 #include "integrate.hpp"
@@ -39,10 +40,7 @@ namespace hpsdf {
 
 namespace {
 
-constexpr unsigned kClrThreads = 256;
 constexpr int kClrSums = 6;  // minFinal, minSplit, outside, pruned, split, final
-
-inline uint32_t clrBlocks(uint32_t n) { return (n + kClrThreads - 1) / kClrThreads; }
 
 // the call's state in device memory: written by the last pass of the two reductions, read back once a level
 struct ClearanceState {
@@ -51,16 +49,6 @@ struct ClearanceState {
     uint32_t hasWitness;
     double sums[kClrSums];
     uint32_t notFinite, pad;
-};
-
-// boundsWalkRange's Stack in LDS: level d of this lane at [d * kClrThreads + lane]
-struct LdsClrStack {
-    uint32_t* f;
-    uint8_t* m;
-    __device__ __forceinline__ uint32_t first(int d) const { return f[d * kClrThreads]; }
-    __device__ __forceinline__ uint32_t mask(int d) const { return m[d * kClrThreads]; }
-    __device__ __forceinline__ void setFirst(int d, uint32_t v) { f[d * kClrThreads] = v; }
-    __device__ __forceinline__ void setMask(int d, uint32_t v) { m[d * kClrThreads] = (uint8_t)v; }
 };
 
 // v of lane t + N of the same row of 16 lanes (DPP row_shl:N); a lane whose source falls outside its row gets 0

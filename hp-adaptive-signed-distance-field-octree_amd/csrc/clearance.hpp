@@ -1,8 +1,8 @@
 // Clearance (include/hpsdf.h, "Clearance"): the plain C++ part -- a cell's bound and witness value, the prune test, the level loop and
 // the result.  Integrate's cells and lists (integrate.hpp), IntegratePair's pose, image box, clamp and point descent (integrate_pair.hpp)
-// and QueryBounds' walk (tree_bound.hpp) are used as they are.  Shared by clearance.hip (the kernels) and clearance_host.cpp (the same
-// loop over host lists): one set of statements with a fixed association, built with -ffp-contract=off, so host and device give the
-// same bits.  No HIP compiler is needed for this file.
+// and QueryBounds' walk (tree_bound.hpp) are used as they are.  Shared by clearance.hip (the kernels), clearance_batch.hip (the
+// kernels of many poses at once) and clearance_host.cpp (the same loop over host lists): one set of statements with a fixed association,
+// built with -ffp-contract=off, so host and device give the same bits.  No HIP compiler is needed for this file.
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -20,6 +20,7 @@ namespace hpsdf {
 struct ClearanceArgs {
     uint32_t depth, maxCells;
     double tol;
+    double decide = boundsQuietNaN();  // the batch entries' decision threshold (a quiet NaN: off, the single call's rule)
 };
 
 // what a level's first kernel leaves of a cell: blo (step 1) and, for a candidate, vb and va (step 2; vb = +inf: no candidate)
@@ -36,6 +37,21 @@ struct ClearanceCandidate {
 constexpr uint32_t kClearanceNoPos = 0xFFFFFFFFu;
 
 __host__ __device__ inline bool clearanceBefore(double vb, uint32_t pos, double wb, uint32_t qos) { return vb < wb || (vb == wb && pos < qos); }
+
+// An order-preserving 64-bit key of a double that is not a NaN: clearanceKey(x) < clearanceKey(y) iff x < y, and equal keys iff x == y
+// (-0.0 and +0.0 share a key, as they compare equal).  What the batch's integer atomicMin reduces (clearance_batch.hip); the least key
+// of a pose and then the least pos among its holders is clearanceBefore's minimum.
+__host__ __device__ inline uint64_t clearanceKey(double x) {
+    if (x == 0.0) x = 0.0;  // -0.0 -> +0.0
+    const uint64_t u = __builtin_bit_cast(unsigned long long, x);
+    return (u >> 63) != 0u ? ~u : u | 0x8000000000000000ull;
+}
+constexpr uint64_t kClearanceNoKey = ~0ull;  // above every key of a double that is not a NaN: the start of a minimum
+// the double of a key (+0.0 for either zero); kClearanceNoKey: +inf, an empty minimum
+__host__ __device__ inline double clearanceKeyValue(uint64_t key) {
+    if (key == kClearanceNoKey) return boundsInf();
+    return __builtin_bit_cast(double, (unsigned long long)((key >> 63) != 0u ? key & 0x7FFFFFFFFFFFFFFFull : ~key));
+}
 
 // Steps 1 and 2 of a cell.  *finite: false if A's cell or a leaf of B's walk is not finite.
 template <class Eval, class Stack>
@@ -100,64 +116,105 @@ inline void clearanceNotFinite(uint32_t levels, hpsdf_clearance* r) {
     r->status = HPSDF_CLEARANCE_NOT_FINITE, r->levels = levels;
 }
 
+// The state of the level loop between two lists, and step 3's last lines on it (include/hpsdf.h, "Clearance", "The rule"): one set of
+// statements for clearanceLevels and for the batch's decide kernel (clearance_batch.hip), a lane a pose.
+struct ClearanceLoop {
+    double finalsLo;           // the least blo of the finals so far (+inf: none)
+    uint64_t nFinals;
+    uint64_t visited, outside, pruned;
+    uint32_t status, levels;
+};
+__host__ __device__ inline void clearanceLoopStart(ClearanceLoop& s) {
+    s.finalsLo = boundsInf();
+    s.nFinals = s.visited = s.outside = s.pruned = 0;
+    s.status = HPSDF_CLEARANCE_EMPTY, s.levels = 0;
+}
+// the first lines of a level: its n cells were visited
+__host__ __device__ inline void clearanceLoopVisit(ClearanceLoop& s, int level, uint32_t n) {
+    s.visited += n;
+    s.levels = (uint32_t)level;
+}
+enum { kClearLoopEmpty = 0, kClearLoopStop = 1, kClearLoopSplit = 2 };
+// A finite level's counts and minima with the updated best -> kClearLoopEmpty: nothing is left and nothing was, the status stays EMPTY;
+// kClearLoopStop: s.status says why, the split candidates join the finals; kClearLoopSplit: their children form the next list.
+__host__ __device__ inline int clearanceLoopStep(ClearanceLoop& s, const ClearanceArgs& a, double best, double minFinal, double minSplit,
+                                                 uint64_t nOutside, uint64_t nPruned, uint64_t nSplit, uint64_t nFinal) {
+    s.outside += nOutside;
+    s.pruned += nPruned;
+    if (s.nFinals == 0 && nFinal == 0 && nSplit == 0) return kClearLoopEmpty;
+    double Lmin = s.finalsLo;
+    if (minFinal < Lmin) Lmin = minFinal;
+    if (minSplit < Lmin) Lmin = minSplit;
+    bool split = false;
+    if (best - Lmin <= a.tol) s.status = HPSDF_CLEARANCE_CONVERGED;
+    else if (Lmin > a.decide || best < a.decide) s.status = HPSDF_CLEARANCE_DECIDED;  // (both false when decide is a NaN)
+    else if (8ull * nSplit > a.maxCells) s.status = HPSDF_CLEARANCE_CELL_LIMIT;
+    else if (nSplit == 0) s.status = HPSDF_CLEARANCE_DEPTH;
+    else split = true;
+    s.nFinals += nFinal + (split ? 0u : nSplit);
+    if (minFinal < s.finalsLo) s.finalsLo = minFinal;
+    if (!split && minSplit < s.finalsLo) s.finalsLo = minSplit;
+    return split ? kClearLoopSplit : kClearLoopStop;
+}
+
+// The struct of a call whose loop ended in s with a status other than NOT_FINITE; cells_open and the finals with blo > hi (which join
+// cells_pruned) are the caller's to add.
+inline void clearanceResult(const ClsTree& tA, const PairArgs& p, const ClearanceLoop& s, double best, double bestVa, const IntegrateCell& bestCell,
+                            uint32_t hasWitness, hpsdf_clearance& r) {
+    const double inf = boundsInf(), nan = boundsQuietNaN();
+    std::memset(&r, 0, sizeof r);
+    r.cells_visited = s.visited, r.cells_outside_a = s.outside, r.cells_pruned = s.pruned;
+    r.levels = s.levels;
+    r.status = s.status;
+    r.value_a = nan;
+    for (int k = 0; k < 3; ++k) r.point[k] = r.image[k] = nan;
+    if (s.status == HPSDF_CLEARANCE_EMPTY) {
+        r.lo = r.hi = inf;
+        return;
+    }
+    r.hi = best;
+    r.lo = s.finalsLo;
+    if (hasWitness) {
+        double x[3], hx[3], y[3];
+        pairCellCentre(tA, p, bestCell, x, hx);
+        pairImage(p, x, y);
+        for (int k = 0; k < 3; ++k) r.point[k] = x[k], r.image[k] = y[k];
+        r.value_a = bestVa;
+    }
+}
+
 // The level loop and the result (include/hpsdf.h, "Clearance", "The rule").  Lists:
 //   level(l, n, &v)                          steps 1 to 3 over the n cells of the current list: v
 //   emit(l, n, split, nSplit, nFinal, cells, blo)   split: the split candidates' children become the current list and the nFinal finals
 //                                            are appended to *cells (may be null) and blo; else all nSplit + nFinal survivors are
 template <class Lists>
 int clearanceLevels(Lists& L, const ClsTree& tA, const PairArgs& p, const ClearanceArgs& a, uint32_t n0, bool wantCells, ClearanceSums& S) {
-    const double inf = boundsInf(), nan = boundsQuietNaN();
     hpsdf_clearance& r = S.r;
     std::memset(&r, 0, sizeof r);
     ClearanceLevel v;
-    v.best = inf;
-    double finalsLo = inf;
-    uint64_t nFinals = 0;
+    v.best = boundsInf();
+    ClearanceLoop s;
+    clearanceLoopStart(s);
     uint32_t n = n0;
-    uint32_t status = HPSDF_CLEARANCE_EMPTY;
     for (int level = 0; n != 0; ++level) {
         if (const int rc = L.level(level, n, &v)) return rc;
-        r.cells_visited += n;
-        r.levels = (uint32_t)level;
+        clearanceLoopVisit(s, level, n);
         if (!v.finite) {
-            clearanceNotFinite(r.levels, &r);
+            clearanceNotFinite(s.levels, &r);
             S.cells.clear(), S.blo.clear();
             return HPSDF_OK;
         }
-        r.cells_outside_a += v.nOutside;
-        r.cells_pruned += v.nPruned;
-        if (nFinals == 0 && v.nFinal == 0 && v.nSplit == 0) break;  // EMPTY
-        double Lmin = finalsLo;
-        if (v.minFinal < Lmin) Lmin = v.minFinal;
-        if (v.minSplit < Lmin) Lmin = v.minSplit;
-        bool split = false;
-        if (v.best - Lmin <= a.tol) status = HPSDF_CLEARANCE_CONVERGED;
-        else if (8ull * v.nSplit > a.maxCells) status = HPSDF_CLEARANCE_CELL_LIMIT;
-        else if (v.nSplit == 0) status = HPSDF_CLEARANCE_DEPTH;
-        else split = true;
+        const int step = clearanceLoopStep(s, a, v.best, v.minFinal, v.minSplit, v.nOutside, v.nPruned, v.nSplit, v.nFinal);
+        if (step == kClearLoopEmpty) break;
+        const bool split = step == kClearLoopSplit;
         if (const int rc = L.emit(level, n, split, (uint32_t)v.nSplit, (uint32_t)v.nFinal, wantCells ? &S.cells : nullptr, S.blo)) return rc;
-        nFinals += v.nFinal + (split ? 0u : v.nSplit);
-        if (v.minFinal < finalsLo) finalsLo = v.minFinal;
-        if (!split && v.minSplit < finalsLo) finalsLo = v.minSplit;
         if (!split) break;
         n = 8u * (uint32_t)v.nSplit;
     }
-    r.status = status;
-    r.value_a = nan;
-    for (int k = 0; k < 3; ++k) r.point[k] = r.image[k] = nan;
-    if (status == HPSDF_CLEARANCE_EMPTY) {
-        r.lo = r.hi = inf;
+    clearanceResult(tA, p, s, v.best, v.bestVa, v.bestCell, v.hasWitness, r);
+    if (s.status == HPSDF_CLEARANCE_EMPTY) {
         S.cells.clear(), S.blo.clear();
         return HPSDF_OK;
-    }
-    r.hi = v.best;
-    r.lo = finalsLo;
-    if (v.hasWitness) {
-        double x[3], hx[3], y[3];
-        pairCellCentre(tA, p, v.bestCell, x, hx);
-        pairImage(p, x, y);
-        for (int k = 0; k < 3; ++k) r.point[k] = x[k], r.image[k] = y[k];
-        r.value_a = v.bestVa;
     }
     size_t kept = 0;
     for (size_t i = 0; i < S.blo.size(); ++i) {
@@ -192,8 +249,16 @@ inline int clearanceHandOver(const ClearanceSums& S, hpsdf_clearance* out, hpsdf
 int clearanceArgumentError(const double* pose, double isoA, uint32_t depth, double tol, uint32_t maxCells, uint32_t maxLeaves, const void* out,
                            const void* outCells, const void* outCount);
 
+// what hpsdf_clearance_batch_* reject before anything runs (0: fine): clearanceArgumentError for every pose, decide, max_total_cells, n
+int clearanceBatchArgumentError(const double* poses, size_t n, double isoA, uint32_t depth, double tol, double decide, uint32_t maxCells,
+                                uint32_t maxLeaves, uint32_t maxTotalCells, const void* out);
+
 // Clearance on the calling thread over the host arrays of tA and tB (clearance_host.cpp)
 int hostClearance(const ClsTree& tA, size_t nNodesA, const ClsTree& tB, const PairArgs& p, const ClearanceArgs& a, hpsdf_clearance* out,
                   hpsdf_integrate_cell** outCells, uint64_t* outCount);
+
+// the batch on the calling thread: hostClearance for every pose with a.decide; out is written only when every pose succeeded
+int hostClearanceBatch(const ClsTree& tA, size_t nNodesA, const ClsTree& tB, const double* poses, size_t n, double isoA, uint32_t maxLeaves,
+                       const ClearanceArgs& a, hpsdf_clearance* out);
 
 }  // namespace hpsdf

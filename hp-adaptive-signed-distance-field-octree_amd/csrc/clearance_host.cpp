@@ -104,7 +104,51 @@ int clearanceArgumentError(const double* pose, double isoA, uint32_t depth, doub
     return HPSDF_OK;
 }
 
+// what hpsdf_clearance_batch_* reject before anything runs (0: fine).  n == 0 is the caller's to answer first.
+int clearanceBatchArgumentError(const double* poses, size_t n, double isoA, uint32_t depth, double tol, double decide, uint32_t maxCells,
+                                uint32_t maxLeaves, uint32_t maxTotalCells, const void* out) {
+    if (n > ((size_t)1 << 24)) return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance_batch: n must be at most 2^24");
+    if (!poses) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const int rc = clearanceArgumentError(poses, isoA, depth, tol, maxCells, maxLeaves, out, nullptr, nullptr)) return rc;
+    if (!(decide != decide || std::fabs(decide) <= DBL_MAX))
+        return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance_batch: decide must be finite or a NaN");
+    if (maxTotalCells < maxCells || maxTotalCells > (1u << 28))
+        return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance_batch: max_total_cells must be in max_cells..2^28");
+    for (size_t i = 1; i < n; ++i)
+        for (int k = 0; k < 12; ++k)
+            if (!(std::fabs(poses[12 * i + k]) <= DBL_MAX))
+                return fail(HPSDF_ERR_INVALID_ARGUMENT, "hpsdf_clearance_batch: every entry of every pose must be finite");
+    return HPSDF_OK;
+}
+
+int hostClearanceBatch(const ClsTree& tA, size_t nNodesA, const ClsTree& tB, const double* poses, size_t n, double isoA, uint32_t maxLeaves,
+                       const ClearanceArgs& a, hpsdf_clearance* out) {
+    std::vector<hpsdf_clearance> res(n);  // (a failure half way writes nothing)
+    for (size_t i = 0; i < n; ++i) {
+        const PairArgs p = pairArgs(tA, HPSDF_PAIR_INTERSECTION, poses + 12 * i, isoA, 0.0, maxLeaves);
+        if (const int rc = hostClearance(tA, nNodesA, tB, p, a, &res[i], nullptr, nullptr)) return rc;
+    }
+    std::memcpy(out, res.data(), n * sizeof(hpsdf_clearance));
+    return HPSDF_OK;
+}
+
 }  // namespace hpsdf
+
+// ClearanceBatch from two serialised blocks, on the calling thread (no device): a loop of the single call with `decide`
+extern "C" int hpsdf_clearance_batch_block(const void* block_a, size_t size_a, const void* block_b, size_t size_b, const double* poses, size_t n,
+                                           double iso_a, uint32_t depth, double tol, double decide, uint32_t max_cells, uint32_t max_leaves,
+                                           uint32_t max_total_cells, hpsdf_clearance* out) {
+    using namespace hpsdf;
+    HPSDF_TRY
+    if (n == 0) return HPSDF_OK;
+    if (const int rc = clearanceBatchArgumentError(poses, n, iso_a, depth, tol, decide, max_cells, max_leaves, max_total_cells, out)) return rc;
+    HostTree hA, hB;
+    if (const int rc = parseBlock(block_a, size_a, &hA)) return rc;
+    if (const int rc = parseBlock(block_b, size_b, &hB)) return rc;
+    const ClearanceArgs a{depth, max_cells, tol, decide};
+    return hostClearanceBatch(hA.view, hA.m.recs.size(), hB.view, poses, n, iso_a, max_leaves, a, out);
+    HPSDF_CATCH
+}
 
 // Clearance from two serialised blocks, on the calling thread (no device): list 0 from A's records, both trees' constants from leafBound
 // on the host

@@ -92,6 +92,11 @@ int integratePairOnDevice(hpsdf_ctx* ctx, const ClsTree& tA, const ClsTree& tB, 
 struct ClearanceArgs;  // clearance.hpp
 int clearanceOnDevice(hpsdf_ctx* ctx, const ClsTree& tA, const ClsTree& tB, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves,
                       const PairArgs& p, const ClearanceArgs& a, hpsdf_clearance* out, hpsdf_integrate_cell** outCells, uint64_t* outCount);
+// ---- ClearanceBatch (clearance_batch.hip): Clearance for n poses (n x 12 doubles, host memory) in lockstep over one list; `out` (n
+// structs) is written only when every pose succeeded
+int clearanceBatchOnDevice(hpsdf_ctx* ctx, const ClsTree& tA, const ClsTree& tB, int maxDegree, const IntegrateCell* dLeaves, uint32_t nLeaves,
+                           const double* poses, size_t n, double isoA, uint32_t maxLeaves, const ClearanceArgs& a, uint32_t maxTotalCells,
+                           hpsdf_clearance* out);
 // ---- the bit-exact fit (fit.hip; its kernels: fit_kernels.hpp, instantiated by fit_analytic.hip, fit_samples.hip, fit_mesh.hip)
 constexpr size_t kFitMaxLdsBytes = 60 * 1024;  // stays under the 64 KiB default dynamic-LDS limit
 constexpr int kFitBlockThreads = 256;

@@ -1043,14 +1043,34 @@ HPSDF_API int hpsdf_integrate_pair_block(const void* block_a, size_t size_a, con
  * updates best in device memory, a prune kernel, a rocPRIM scan, one read-back and an emit kernel -- and synchronises before it returns;
  * no atomic decides a value.  _host computes on the calling thread from the trees' host copies, _block from two serialised blocks with
  * no device at all.
- * Not done: maximisation; batches of poses in one call; subdiv above 1 on B; upper bounds without a witness (an inside cell's walk
- * gives a hi that no sample attains); best-first ordering of the cells; contact normals (call QueryGradient of B at `image`). */
+ * Batches.  hpsdf_clearance_batch_* answer n poses of the same two trees in one call: poses holds n x 12 doubles, out n structs, and
+ * iso_a, depth, tol, max_cells and max_leaves are shared.  Every pose runs the rule above on its own -- pos is a cell's position in its
+ * own pose's list -- and out[i] equals, byte for byte, what the single call returns for pose i; it does not depend on the other poses,
+ * on their order or on max_total_cells.  One addition to the rule, the decision threshold `decide` (a quiet NaN: off; the single
+ * entries run with it off): in step 3, after the test best - L <= tol and before the cell-limit test,
+ *              L > decide or best < decide:         status HPSDF_CLEARANCE_DECIDED, the split candidates join finals, stop
+ * L > decide proves that every point of A's solid has a B-value above decide, best < decide is a witness below it; the enclosure is
+ * as guaranteed as any other, only wider than the full search's.  Arguments: those of the single call for every pose; decide finite or
+ * a NaN; n <= 2^24 (n == 0 returns HPSDF_OK, writes nothing, and poses and out may be NULL); max_total_cells in max_cells .. 2^28, the
+ * most cells the lists of all poses of one pass hold together.  The device entry takes the poses in chunks whose lists 0 fit that
+ * budget (a single pose is always admitted); a chunk whose next list would not fit is halved and its parts start again from list 0.
+ * On the device the lists of a chunk's poses are one list (a pose's cells contiguous, in the single call's order, with a parallel pose
+ * index) and the levels run in lockstep: per level a bound kernel, a kernel that finds each pose's (vb, pos) minimum, a prune kernel,
+ * a kernel that runs step 3's last lines a lane a pose, a kernel that writes the scan's words, one rocPRIM scan over the cells, an emit kernel and one read-back of two
+ * totals -- a number of launches that does not depend on n.  The per-pose minima and counts are integer atomics (a minimum over an
+ * order-preserving key of the double, then over pos; sums of counts): no result depends on the order of execution.  Batches do not
+ * return cells.  hpsdf_clearance_batch_host and _block are a loop of the single call's host path with `decide`.
+ * On HPSDF_ERR_INVALID_ARGUMENT nothing is written.
+ * Not done: maximisation; cells from a batch (batches of poses return the structs only); subdiv above 1 on B; upper bounds
+ * without a witness (an inside cell's walk gives a hi that no sample attains); best-first ordering of the cells; contact normals
+ * (call QueryGradient of B at `image`). */
 enum {
     HPSDF_CLEARANCE_CONVERGED = 0,
     HPSDF_CLEARANCE_DEPTH = 1,
     HPSDF_CLEARANCE_CELL_LIMIT = 2,
     HPSDF_CLEARANCE_EMPTY = 3,
-    HPSDF_CLEARANCE_NOT_FINITE = 4
+    HPSDF_CLEARANCE_NOT_FINITE = 4,
+    HPSDF_CLEARANCE_DECIDED = 5 /* the batch entries' `decide` only */
 };
 typedef struct hpsdf_clearance { /* 112 bytes */
     double lo, hi;            /* lo <= m <= hi */
@@ -1073,6 +1093,15 @@ HPSDF_API int hpsdf_clearance_host(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, con
 HPSDF_API int hpsdf_clearance_block(const void* block_a, size_t size_a, const void* block_b, size_t size_b, const double pose[12], double iso_a,
                                     uint32_t depth, double tol, uint32_t max_cells, uint32_t max_leaves, hpsdf_clearance* out,
                                     hpsdf_integrate_cell** out_cells, uint64_t* out_n_cells);
+HPSDF_API int hpsdf_clearance_batch_device(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, const hpsdf_tree* tree_b, const double* poses, size_t n,
+                                           double iso_a, uint32_t depth, double tol, double decide, uint32_t max_cells, uint32_t max_leaves,
+                                           uint32_t max_total_cells, hpsdf_clearance* out);
+HPSDF_API int hpsdf_clearance_batch_host(hpsdf_ctx* ctx, const hpsdf_tree* tree_a, const hpsdf_tree* tree_b, const double* poses, size_t n,
+                                         double iso_a, uint32_t depth, double tol, double decide, uint32_t max_cells, uint32_t max_leaves,
+                                         uint32_t max_total_cells, hpsdf_clearance* out);
+HPSDF_API int hpsdf_clearance_batch_block(const void* block_a, size_t size_a, const void* block_b, size_t size_b, const double* poses, size_t n,
+                                          double iso_a, uint32_t depth, double tol, double decide, uint32_t max_cells, uint32_t max_leaves,
+                                          uint32_t max_total_cells, hpsdf_clearance* out);
 
 /* ---- Simplify: hp-coarsen a built tree within an RMS bound (no reference counterpart) ---------------------------------------------------
  * Makes a NEW tree from a serialised one: sibling leaves are merged into their parent (h-coarsening) and top degrees are dropped

@@ -804,6 +804,21 @@ class Octree {
         return r;
     }
 
+    /// Clearance for n_ poses (poses_: n_ x 12 doubles) in one device call (include/hpsdf.h, "Clearance", "Batches"): element i is,
+    /// byte for byte, Clearance(other_, poses_ + 12 i, ...)'s struct.  decide_ (a quiet NaN: off) stops a pose with
+    /// HPSDF_CLEARANCE_DECIDED as soon as lo > decide_ or hi < decide_ is proven; maxTotalCells_ bounds the cells of all poses' lists
+    /// of one pass together.  Batches return no cells.
+    std::vector<hpsdf_clearance> ClearanceBatch(const Octree& other_, const double* poses_, size_t n_, f64 isoA_ = 0.0, uint32_t depth_ = 10,
+                                                f64 tol_ = 0.0, uint32_t maxCells_ = 1u << 24, uint32_t maxLeaves_ = 256,
+                                                f64 decide_ = std::numeric_limits<f64>::quiet_NaN(), uint32_t maxTotalCells_ = 1u << 24) const {
+        hpsdf_tree* t = deviceTree();
+        hpsdf_tree* o = other_.deviceTree();
+        if (!t || !o) throw Error(HPSDF_ERR_STATE, "Query on an empty octree");
+        std::vector<hpsdf_clearance> r(n_);
+        check(hpsdf_clearance_batch_device(ctx_, t, o, poses_, n_, isoA_, depth_, tol_, decide_, maxCells_, maxLeaves_, maxTotalCells_, r.data()));
+        return r;
+    }
+
     /// A NEW octree within rms_ of this one, leaf cell by leaf cell, in the root-normalised L2 sense (no reference counterpart;
     /// include/hpsdf.h, "Simplify"): sibling leaves merged into their parent (HPSDF_SIMPLIFY_MERGE) and top degrees dropped
     /// (HPSDF_SIMPLIFY_TRUNCATE) from the coefficients alone -- no field is sampled --, every result cell C with
