@@ -449,6 +449,9 @@ class Context:
         return data
 
     def set_stream(self, stream):
+        """Moves the context to another stream (raw hipStream_t; None: the null stream).  What the context queues afterwards runs behind
+        everything queued on the old stream so far, without a host wait; a library-owned old stream is synchronised and destroyed
+        (include/hpsdf.h, "The stream contract")."""
         check(lib().hpsdf_ctx_set_stream(self.handle, C.c_void_p(stream) if stream else None))
 
     def set_reduction_order(self, left_assoc):

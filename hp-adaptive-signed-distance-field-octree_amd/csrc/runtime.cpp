@@ -255,12 +255,24 @@ int hpsdf_ctx_destroy(hpsdf_ctx* c) {
 
 int hpsdf_ctx_set_stream(hpsdf_ctx* c, void* stream) {
     if (!c) return fail(HPSDF_ERR_INVALID_ARGUMENT, "null ctx");
+    hipStream_t next = (hipStream_t)stream;
+    if (next == c->stream) return HPSDF_OK;  // (also the owned stream handed back: it stays, and stays owned)
+    HPSDF_HIP(hipSetDevice(c->device));
     if (c->ownsStream && c->stream) {
         (void)hipStreamSynchronize(c->stream);
         (void)hipStreamDestroy(c->stream);
         c->ownsStream = false;
+    } else {
+        // What the context has queued on the caller's old stream may still be running, on scratch that its next call shares (Query's
+        // deferred lists, the *_host entries' buffers, the build's workspace): the new stream starts behind it.  No host wait.
+        hipEvent_t done = nullptr;
+        HPSDF_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(done, c->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(next, done, 0);
+        (void)hipEventDestroy(done);  // (released once the wait has been served)
+        if (e != hipSuccess) return hipFail(e, "hpsdf_ctx_set_stream: ordering the new stream behind the old one");
     }
-    c->stream = (hipStream_t)stream;
+    c->stream = next;
     return HPSDF_OK;
 }
 

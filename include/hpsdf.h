@@ -116,7 +116,24 @@ typedef struct hpsdf_ctx hpsdf_ctx;
  * vectors and worker threads -- all kept between calls): hpsdf_create, the hpsdf_build_* round calls and
  * hpsdf_continuity_post_process_device use one context from one thread at a time.  The *_host query entry points
  * serialise themselves per context (Octree::Query* is const and callable from many threads in the reference);
- * use one context per thread for concurrent builds. */
+ * use one context per thread for concurrent builds.
+ *
+ * The stream contract.  Every *_device entry launches on the context's stream and nowhere else, in the order of the calls: inputs that
+ * earlier work on that stream produces are read after it, outputs are complete for later work on that stream, and the context's own
+ * scratch is reused in stream order.  Entries documented as asynchronous return without waiting for the stream, with two exceptions
+ * that wait on the host because memory changes hands: the first bounds, Integrate, IntegratePair or Clearance call on a tree (it builds
+ * the tree's cached constants on the context's stream and waits for them, so that a call on any other stream finds them complete),
+ * and a Query on a tree with leaves of degree > 3 that has more points than any such Query of the context before it (the deferred-point
+ * scratch is freed and taken again, and freeing device memory waits for the device).  Entries that return host results (Integrate,
+ * IntegratePair, Clearance, ClearanceBatch, Simplify, ExtractSurface*, Create, every *_host entry) wait for the stream before they
+ * return.  A library-owned stream is non-blocking: it does not synchronise with the null stream.
+ *
+ * hpsdf_ctx_set_stream moves the context to another stream (NULL: the device's null stream).  Work the context queues afterwards runs
+ * behind everything that was queued on the old stream when set_stream was called, the caller's own work included: an event recorded on
+ * the old stream is waited for by the new one, with no host wait, so the scratch the two share is never used by both at once.  The old
+ * stream must still exist at that moment.  When the old stream is the library-owned one it is synchronised on the host and destroyed
+ * instead; the pointer hpsdf_ctx_stream returned before is dead from then on.  The context never owns a stream it was given, and
+ * setting the stream it already has (its own included) changes nothing. */
 HPSDF_API int hpsdf_ctx_create(int device, void* stream, hpsdf_ctx** out);
 HPSDF_API int hpsdf_ctx_destroy(hpsdf_ctx* ctx);
 HPSDF_API int hpsdf_ctx_set_stream(hpsdf_ctx* ctx, void* stream);
@@ -770,8 +787,9 @@ HPSDF_API int hpsdf_surface_dual_last_timings(double ms[8]);
  * box entries' bits for the same corners.
  * A NULL tree, a required array NULL with n > 0 (grid: NULL lo, hi or n), subdiv not 1, 2 or 4, max_leaves outside 1..65535, a
  * lattice hpsdf_extract_surface would refuse: HPSDF_ERR_INVALID_ARGUMENT, and no output is written.  n == 0 is HPSDF_OK.  _device is
- * asynchronous on the context stream (the first bounds call on a tree builds the leaves' constants G_a, S once, under a lock, and keeps
- * them with the tree until hpsdf_tree_destroy: 32 bytes a node; every later call only launches); _host answers calls of up to 32
+ * asynchronous on the context stream, except that the first bounds call on a tree builds the leaves' constants G_a, S once, under a
+ * lock, on the context stream, and WAITS for that stream on the host before it launches (a call on another stream must find them
+ * complete); it keeps them with the tree until hpsdf_tree_destroy: 32 bytes a node; every later call only launches; _host answers calls of up to 32
  * boxes on the calling thread and sends larger ones through the device; _block needs no device: it works from a serialised block on
  * the calling thread and accepts and refuses blocks as hpsdf_project_block does.
  * Not done: boxes reaching outside the root are INVALID, not clipped; a large box is one lane's walk (see max_leaves); the enclosure
